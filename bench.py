@@ -18,7 +18,8 @@ figure is reported as `round_trip_traffic_GiB_per_s`, never as `value`.)
 
 Synthetic input: keys = 16 B big-endian counters, values 64 B
 uniform random, seqno 63, all Value, cut by the writer rule at 4096 B (52 items /
-3769-3773 B per block), restart interval 16, hash ratio 0.  Outside the timed
+3769-3773 B per block), restart interval 16, hash ratio 0; the seeds are fixed,
+so the inputs are the same from run to run.  With --full, outside the timed
 region EVERY block is checked: encoded bytes == the oracle's encode (memcmp),
 decoded fields == the oracle's decode (multithreaded oracle on the host).
 
@@ -26,7 +27,12 @@ N > 1: one process per GPU (torch.distributed, RCCL only for the max-time /
 byte-sum reductions), each rank round-trips its own 1 M-block batch (weak
 scaling, no data-path collective).
 
-Also in the same JSON line (not `value`): per-kernel rooflines (decode, encode)
+A plain run sets up, warms up, times the K steps and prints the result line
+(metric, value, ms_per_step, ...); nothing else runs.  --dump-outputs DIR then
+writes what the last timed step returned (dump_outputs below).
+
+--full adds the every-block oracle check above and,
+also in the same JSON line (not `value`): per-kernel rooflines (decode, encode)
 with the measured copy / LDS-DMA read ceilings, configs[3] (prefix-heavy 16 KiB),
 configs[4] (8 GiB mixed 4/16/64 KiB data + index blocks byte-split across ranks),
 point reads, range seeks, whole-file checksum, Bloom filter, LZ4 (and the
@@ -186,6 +192,57 @@ def check_decode_all(dec, ref_buf, ref_off, nb, threads, fields=DATA_FIELDS, exp
         g = dec[f][:n].cpu().numpy().view(FIELD_NP[f])
         assert np.array_equal(g, parsed[f].astype(FIELD_NP[f])), f"decoded field {f} differs from the oracle"
     return n
+
+
+# ------------------------------------------------------------ --dump-outputs
+DUMP_SAMPLE_BLOCKS = 1024  # ~17 KB of float32 / float64 per sampled 4 KiB block
+DUMP_CHUNK = 1 << 16       # elements per chunk sum
+DUMP_SEED = 0x5EED00D0
+
+
+def dump_outputs(torch, path, enc, out, nb, n_items, rank=0):
+    """What the timed step's caller holds after the last step, as <path>/<name>.npy
+    (float64 where a value may pass 2^24, float32 otherwise), ~45 MB at 1 M blocks:
+      enc_block_off, enc_status, dec_item_start, dec_status   whole, one entry per block;
+      enc_buf_chunk_sums, dec_<field>_chunk_sums               every output byte / item, as
+                                                               int64 sums over DUMP_CHUNK elements;
+      sample_blocks                                            the same seeded block ids every run;
+      enc_buf_sample, dec_<field>_sample                       those blocks' encoded bytes and their
+                                                               items' decoded fields, concatenated
+                                                               in sample_blocks order.
+    Ranks above 0 write <name>.rank<r>.npy."""
+    import numpy as np
+    d = Path(path)
+    d.mkdir(parents=True, exist_ok=True)
+    sfx = "" if rank == 0 else f".rank{rank}"
+
+    def save(name, t, dt):
+        a = t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
+        np.save(d / f"{name}{sfx}.npy", a.astype(dt))
+
+    def chunk_sums(t):
+        m = t.numel() // DUMP_CHUNK * DUMP_CHUNK
+        parts = [t[:m].view(m // DUMP_CHUNK, DUMP_CHUNK).sum(dim=1, dtype=torch.int64)]
+        if m < t.numel():
+            parts.append(t[m:].sum(dtype=torch.int64).reshape(1))
+        return torch.cat(parts)
+
+    off = enc["block_off"][:nb + 1].cpu()
+    ist = out["item_start"][:nb + 1].cpu()
+    total = int(off[nb])
+    save("enc_block_off", off, np.float64)
+    save("enc_status", enc["status"][:nb], np.float32)
+    save("dec_item_start", ist, np.float64)
+    save("dec_status", out["status"][:nb], np.float32)
+    save("enc_buf_chunk_sums", chunk_sums(enc["buf"][:total]), np.float64)
+    ids = np.sort(np.random.RandomState(DUMP_SEED).choice(nb, size=min(DUMP_SAMPLE_BLOCKS, nb), replace=False))
+    save("sample_blocks", ids, np.float64)
+    save("enc_buf_sample", torch.cat([enc["buf"][int(off[b]):int(off[b + 1])] for b in ids]), np.float32)
+    n = min(n_items, int(ist[nb]))
+    for f in DATA_FIELDS:
+        dt = np.float64 if f == "seqno" else np.float32
+        save(f"dec_{f}_chunk_sums", chunk_sums(out[f][:n]), np.float64)
+        save(f"dec_{f}_sample", torch.cat([out[f][int(ist[b]):int(ist[b + 1])] for b in ids]), dt)
 
 
 # ------------------------------------------------------------- CPU baseline
@@ -1257,6 +1314,12 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--blocks", type=int, default=1 << 20)
+    ap.add_argument("--full", action="store_true",
+                    help="also check every block against the oracle and measure everything beside the headline "
+                         "(rooflines, each direction alone, the other configs and side legs, host-inclusive rates, "
+                         "the CPU baseline); the --no-* / --skip-verify switches below trim such a run")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-host", action="store_true", help="skip the host-inclusive (PCIe) measurements")
     ap.add_argument("--cpu-seconds", type=float, default=2.0, help="minimum seconds per CPU baseline leg")
@@ -1321,7 +1384,7 @@ def main():
     step()
     torch.cuda.synchronize()
     ref_buf = ref_off = items_host = starts_np = None
-    if not args.skip_verify:
+    if args.full and not args.skip_verify:
         t_chk = time.perf_counter()
         ref_buf, ref_off = check_encode_all(torch, items, starts, enc, nb, n_items, threads)
         check_decode_all(out, ref_buf, ref_off, nb, threads)
@@ -1353,6 +1416,55 @@ def main():
         all_bytes = total_bytes
     ms_per_step = el * 1e3 / args.steps
     value = all_bytes * args.steps / el / 2 ** 30
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, enc, out, nb, n_items, rank)
+
+    if not args.full:
+        verified = "not checked against the oracle in this run (--full checks every block)"
+    elif args.skip_verify:
+        verified = "skipped"
+    else:
+        verified = f"all {nb} blocks per rank bit-exact vs the oracle (encoded bytes and every decoded field)"
+    line = {
+        "metric": BASELINE_METRIC,
+        "value": round(value, 3),
+        "unit": "GiB/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": f"synthetic (16 B BE-counter keys, 64 B random values, seqno 63); {verified}",
+        "config": {"workload": "BASELINE configs[1]/[2]: encode + decode round trip of 1 M x 4 KiB data blocks, "
+                               "device-resident",
+                   "blocks_per_gpu": nb, "items_per_gpu": n_items, "block_bytes_per_gpu": total_bytes,
+                   "restart_interval": 16, "hash_ratio": 0.0, "key_len": 16, "val_len": 64,
+                   "step": "lsm_encode_blocks32 (item SoA, u32 offsets -> blocks) + lsm_decode_blocks "
+                           "(blocks -> parsed SoA)",
+                   "parallelism": f"shard{world} (independent block batches, no collective)"},
+        "round_trip_traffic_GiB_per_s": round(2 * value, 3),
+        "gpu_event_ms_per_step": round(gpu_ms / args.steps, 4),
+    }
+    if rehearse:  # every rank on cuda:0: a rehearsal of the N > 1 path, never a multi-GPU measurement
+        line["rehearsal"] = True
+        line["physical_gpus"] = 1
+        line["data"] += f"; REHEARSAL: {world} ranks shared one GPU, not a multi-GPU measurement"
+    if dist is not None:
+        line["process_group"] = {"backend": dist.get_backend(), "world_size": dist.get_world_size()}
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:  # a plain run ends here: everything below takes runs of its own
+        finish()
+        return
 
     # each direction alone, HIP events on its launch stream
     def timed(fn, reps):
@@ -1438,28 +1550,7 @@ def main():
         cpu = cpu_baseline(ref_buf, ref_off, items_host, starts_np, min_seconds=args.cpu_seconds)
 
     if rank == 0:
-        verified = "skipped" if args.skip_verify else f"all {nb} blocks per rank bit-exact vs the oracle (encoded bytes " \
-                                                      f"and every decoded field)"
-        line = {
-            "metric": BASELINE_METRIC,
-            "value": round(value, 3),
-            "unit": "GiB/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": f"synthetic (16 B BE-counter keys, 64 B random values, seqno 63); {verified}",
-            "config": {"workload": "BASELINE configs[1]/[2]: encode + decode round trip of 1 M x 4 KiB data blocks, "
-                                   "device-resident",
-                       "blocks_per_gpu": nb, "items_per_gpu": n_items, "block_bytes_per_gpu": total_bytes,
-                       "restart_interval": 16, "hash_ratio": 0.0, "key_len": 16, "val_len": 64,
-                       "step": "lsm_encode_blocks32 (item SoA, u32 offsets -> blocks) + lsm_decode_blocks "
-                               "(blocks -> parsed SoA)",
-                       "parallelism": f"shard{world} (independent block batches, no collective)"},
+        line.update({
             "roofline": dominant,
             "roofline_decode": r_dec,
             "roofline_encode": r_enc,
@@ -1476,21 +1567,10 @@ def main():
                                "read_only_frac": round(total_bytes / (kdec16_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
                                "note": "lsm_decode_blocks16 (19 B/item: u16 payload offsets / lengths), item_start "
                                        "precomputed; every field equal to the 32-bit decode's"},
-            "round_trip_traffic_GiB_per_s": round(2 * value, 3),
             **extra,
             "host_inclusive": hostinc or None,
-            "gpu_event_ms_per_step": round(gpu_ms / args.steps, 4),
-        }
-        if rehearse:  # every rank on cuda:0: a rehearsal of the N > 1 path, never a multi-GPU measurement
-            line["rehearsal"] = True
-            line["physical_gpus"] = 1
-            line["data"] += f"; REHEARSAL: {world} ranks shared one GPU, not a multi-GPU measurement"
-        if dist is not None:
-            line["process_group"] = {"backend": dist.get_backend(), "world_size": dist.get_world_size()}
-        print(json.dumps(line), flush=True)
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+        })
+    finish()
 
 
 if __name__ == "__main__":
