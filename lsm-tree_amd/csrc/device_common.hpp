@@ -1189,5 +1189,17 @@ __device__ __forceinline__ uint32_t wave_readlane_u32(uint32_t v, uint32_t src) 
 __device__ __forceinline__ uint64_t wave_readlane_u64(uint64_t v, uint32_t src) {
   return (uint64_t)wave_readlane_u32((uint32_t)v, src) | ((uint64_t)wave_readlane_u32((uint32_t)(v >> 32), src) << 32);
 }
+// wave-wide minimum, wave-uniform (SGPR); every lane must be active.  Four DPP
+// steps inside the 16-lane rows (quad perms and row mirrors read an in-range
+// lane for every lane), then the four rows by v_readlane: no LDS round trip.
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+  v = min(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
+  v = min(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, true));   // quad_perm [2,3,0,1]
+  v = min(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x141, 0xF, 0xF, true));  // row_half_mirror
+  v = min(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x140, 0xF, 0xF, true));  // row_mirror
+  const uint32_t r0 = wave_readlane_u32(v, 0), r1 = wave_readlane_u32(v, 16);
+  const uint32_t r2 = wave_readlane_u32(v, 32), r3 = wave_readlane_u32(v, 48);
+  return (uint32_t)__builtin_amdgcn_readfirstlane((int)min(min(r0, r1), min(r2, r3)));
+}
 
 }  // namespace lsmgpu

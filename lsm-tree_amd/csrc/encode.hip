@@ -1404,7 +1404,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void e
 //          stage), record length, workgroup scan -> record offset in block
 //   write  thread = item: its record (header bytes, key suffix, value LEB +
 //          bytes) into the LDS image of the group's output span, binary
-//          index entry, hash-index vote; the next group's DMA is issued
+//          index entry, hash-index vote; the next group's DMA is issued.
+//          The values' interior dwords go wave by wave, in a loop whose trip
+//          count is the wave's shortest interior (lds_copy_uniform); the
+//          edges and what longer values have left, lane by lane (lds_copy)
 //   tails  wave per block: marker, hash-index bytes, trailer
 //   hash   the 16 DPP rows of the workgroup split every block's payload
 //          into 1 KiB units (XXH3 per-KiB contributions, then one short
@@ -1444,8 +1447,11 @@ static_assert(kGRunFused * (sizeof(BlockPlan) + 8) + 16 <= kGUnion, "fused plan 
 // Lane `rot` starts its dword loop at a lane-dependent point of the span and
 // wraps: records with a power-of-two source stride (64 B values: every lane
 // of a 32-lane group on 2 banks) then read and write conflict-free.
+// `done`: the span's first `done` interior dwords are already in place
+// (lds_copy_uniform); the head bytes, the dwords past them and the tail bytes
+// are copied here.
 __device__ __forceinline__ void lds_copy(uint8_t* dst, uint32_t d, const uint8_t* src, uint32_t s, uint32_t n,
-                                         uint32_t rot) {
+                                         uint32_t rot, uint32_t done = 0) {
   if (!n) return;
   // (every read of a step is issued before its writes: one LDS round trip per step)
   const uint32_t h = min(n, (4u - (d & 3u)) & 3u);
@@ -1457,8 +1463,8 @@ __device__ __forceinline__ void lds_copy(uint8_t* dst, uint32_t d, const uint8_t
   for (uint32_t k = 0; k < 3; ++k)
     if (k < h) dst[d + k] = (uint8_t)hb[k];
   if (n == h) return;
-  const uint32_t d1 = d + h, e = d + n, body = ((e & ~3u) - d1) >> 2;
-  const uint32_t sp = s + h, sh = sp & 3u;
+  const uint32_t d1 = d + h + 4 * done, e = d + n, body = ((e & ~3u) - d1) >> 2;
+  const uint32_t sp = s + h + 4 * done, sh = sp & 3u;
   const uint32_t* s32 = reinterpret_cast<const uint32_t*>(src + (sp & ~3u));
   uint32_t* d32 = reinterpret_cast<uint32_t*>(dst + d1);
   // 32 start points: a ds_read_b32 wave access is two groups of 32 lanes, so
@@ -1498,6 +1504,80 @@ __device__ __forceinline__ void lds_copy(uint8_t* dst, uint32_t d, const uint8_t
 #pragma unroll
   for (uint32_t k = 0; k < 3; ++k)
     if (t0 + k < e) dst[t0 + k] = (uint8_t)tb[k];
+}
+
+// The group kernel's value copy, first part: the interior dwords that every
+// value-carrying lane of the wave has, in a loop with a wave-uniform trip count.
+// Lane by lane lds_copy's dword loop tests the wrap, the end of the span and the
+// carry per dword (the spans' dword counts differ between lanes, by one already
+// for equal lengths at different destination alignments), which compiles to an
+// exec-mask write and branches per dword (per 4 dwords 43 VALU, 40 scalar and
+// branch instructions).  Here B, the wave-wide minimum of the lanes' interior
+// dword counts, is in an SGPR: the loop runs ceil(B / 4) steps of 4 dwords, the
+// wrap is min(x, x - B), the exec mask is set once around the loop, and the body
+// has no per-lane condition but a select of the carried source dword at the wrap
+// (32 VALU, under one scalar instruction per 4 dwords).  The rotation is
+// lds_copy's, modulo B.  After the loop a lane with more than B dwords copies one
+// more, so that equal-length values leave lds_copy only their head and tail bytes.
+// Called with every lane active; `has`: this lane copies n > 0 bytes
+// src[s ..) -> dst[d ..).  Returns the lane's number of interior dwords now in
+// place (0: B under kUniformMin, or no lane with `has`), to be handed to lds_copy
+// as `done`.  The bytes written are the same whichever way they are copied.
+// Measured in scripts/exp/lds_copy_bench.cpp (variant 10) and in the kernel:
+// DESIGN §6.7, profiles/uniform_copy_ab.txt.
+#ifdef LSM_NO_UNIFORM_COPY
+constexpr bool kUniformCopy = false;  // (A/B build: the general loop alone)
+#else
+constexpr bool kUniformCopy = true;
+#endif
+constexpr uint32_t kUniformMin = 4;  // dwords per step; fewer than one step: the general loop alone
+__device__ __forceinline__ uint32_t lds_copy_uniform(uint8_t* dst, uint32_t d, const uint8_t* src, uint32_t s,
+                                                     uint32_t n, bool has, uint32_t rot) {
+  if (!kUniformCopy) return 0;
+  const uint32_t h = min(n, (4u - (d & 3u)) & 3u);
+  const uint32_t body = n > h ? (((d + n) & ~3u) - (d + h)) >> 2 : 0u;
+  const uint32_t B = wave_min_u32(has ? body : 0xFFFFFFFFu);
+  if (B < kUniformMin || B == 0xFFFFFFFFu) return 0;
+  if (has) {
+    const uint8_t* sb = src + ((s + h) & ~3u);
+    uint8_t* db = dst + d + h;
+    const uint32_t sh = (s + h) & 3u, B4 = 4 * B;
+    auto ld = [&](uint32_t x) { return *reinterpret_cast<const uint32_t*>(sb + x); };
+    auto st = [&](uint32_t x, uint32_t v) { *reinterpret_cast<uint32_t*>(db + x) = v; };
+    constexpr uint32_t U = kUniformMin;
+    uint32_t x = (((rot & 31u) * B) >> 5) * 4;  // byte offset of the lane's next dword, < B4
+    // destination dword x is alignbyte(src[x + 4], src[x]); src[x] is the dword
+    // carried from the step before, except after the wrap to x = 0 (w0)
+    const uint32_t w0 = ld(0);
+    uint32_t carry = ld(x);
+    // (B is no multiple of U: the last step wraps on over dwords already copied and
+    // stores the same bytes again, which is cheaper than a remainder loop's LDS round
+    // trip per dword)
+    for (uint32_t j = 0; j < B; j += U) {
+      uint32_t at[U], hi[U];
+#pragma unroll
+      for (uint32_t t = 0; t < U; ++t) {
+        const uint32_t y = x + 4 * t;
+        at[t] = t == 0 ? x : min(y, y - B4);  // (y < B4: y - B4 wraps high)
+        hi[t] = ld(at[t] + 4);
+      }
+#pragma unroll
+      for (uint32_t t = 0; t < U; ++t) {
+        const uint32_t lo = at[t] == 0 ? w0 : (t == 0 ? carry : hi[t - 1]);
+        st(at[t], alignbyte(hi[t], lo, sh));
+      }
+      carry = hi[U - 1];
+      x += 4 * U;
+      x = min(x, x - B4);
+    }
+    // one dword more where the lane has it (equal lengths differ by at most this one,
+    // by the destination alignment): lds_copy then finds no dword left and skips its loop
+    if (body > B) {
+      st(B4, alignbyte(ld(B4 + 4), ld(B4), sh));
+      return B + 1;
+    }
+  }
+  return B;
 }
 
 __device__ __forceinline__ uint32_t lds_put_leb(uint8_t* dst, uint32_t pos, uint64_t v) {
@@ -2161,14 +2241,22 @@ __global__ __launch_bounds__(kGThreads) __attribute__((amdgpu_waves_per_eu(4))) 
     // Two writers on purpose: the split one (tsh > 0) also covers tsh = 0, but as
     // the only writer it measured 0.6 % slower on configs[1] and 0.5 % on
     // configs[3] (3.237 vs 3.218 ms, 3.131 vs 3.115 ms; profiles/r03_encode_experiments.txt).
-    // A fix in one must be made in both.
-    if (tsh == 0) {
-    if (live && !(kDiagBuild && (P.diag & 9))) {
-      const GBlk& B = TB[j];
-      const uint32_t roff = m.e & 0x7FFFu;
-      const uint32_t p0 = B.img + kHdrLen;
-      uint32_t pos = p0 + roff;
-      const uint32_t kst = (uint32_t)(m.ko - kbase);
+    // They share the header (put_header), the binary-index entry and hash vote,
+    // and the value copy: once the header is written (for the parts past the first,
+    // once its length is computed) every lane knows where its value goes, so
+    // between the writers' `if (writes)` regions, with every lane active,
+    // lds_copy_uniform copies the interior dwords common to the wave's values
+    // (DESIGN §6.7), and lds_copy finishes each lane's head bytes, surplus dwords
+    // and tail bytes.
+    const bool writes = live && !(kDiagBuild && (P.diag & 9));
+    const uint32_t roff = m.e & 0x7FFFu;
+    const uint32_t from = head ? 0 : m.sh;
+    const uint32_t kst = (uint32_t)(m.ko - kbase);
+    const bool has_val = writes && !index && !is_tombstone(m.vt);
+    const uint32_t vsrc = (uint32_t)(m.vo - vbase);
+    // type byte, varints, key (suffix), value length: up to the value, whose place it returns
+    auto put_header = [&]() -> uint32_t {
+      uint32_t pos = TB[j].img + kHdrLen + roff;
       if (index) {
         L.img[pos++] = 0;
         pos = lds_put_leb(L.img, pos, m.vo);
@@ -2179,71 +2267,21 @@ __global__ __launch_bounds__(kGThreads) __attribute__((amdgpu_waves_per_eu(4))) 
       } else {
         L.img[pos++] = (uint8_t)m.vt;
         pos = lds_put_leb(L.img, pos, m.seq);
-        const uint32_t from = head ? 0 : m.sh;
         if (!head) pos = lds_put_leb(L.img, pos, m.sh);
         pos = lds_put_leb(L.img, pos, m.klen - from);
         lds_copy(L.img, pos, L.keys, kst + from, m.klen - from, lane);
         pos += m.klen - from;
-        if (!is_tombstone(m.vt)) {
-          pos = lds_put_leb(L.img, pos, m.vl);
-          lds_copy(L.img, pos, L.vals, (uint32_t)(m.vo - vbase), m.vl, lane);
-        }
+        if (!is_tombstone(m.vt)) pos = lds_put_leb(L.img, pos, m.vl);
       }
+      return pos;
+    };
+    auto put_index_and_vote = [&]() {
+      const GBlk& B = TB[j];
       if (head) {
-        const uint32_t bp = p0 + B.recs + 1 + (m.e >> 16) * B.step;
+        const uint32_t bp = B.img + kHdrLen + B.recs + 1 + (m.e >> 16) * B.step;
         for (uint32_t q = 0; q < B.step; ++q) L.img[bp + q] = (uint8_t)(roff >> (8 * q));
       }
       if (kHash && B.hash_w) {
-        const uint32_t ridx = (tid - B.it0) / ri;
-        const uint32_t hb =
-            kPlanBkt ? m.hb
-                     : (uint32_t)(xxh3_64_any(m.klen, BaseReader8{L.keys, kst}, BaseReader64{L.keys, kst}) % B.hash_w);
-        const uint32_t bk = B.hash_base + hb;
-        atomicMin(&hlo[bk], ridx);
-        atomicMax(&hhi[bk], ridx);
-      }
-    }
-    } else {
-    if (live && !(kDiagBuild && (P.diag & 9))) {
-      const GBlk& B = TB[j];
-      const uint32_t roff = m.e & 0x7FFFu;
-      const uint32_t p0 = B.img + kHdrLen;
-      uint32_t pos = p0 + roff;
-      const uint32_t kst = (uint32_t)(m.ko - kbase);
-      if (index) {
-        if (part == 0) {
-          L.img[pos++] = 0;
-          pos = lds_put_leb(L.img, pos, m.vo);
-          pos = lds_put_leb(L.img, pos, m.vl);
-          pos = lds_put_leb(L.img, pos, m.seq);
-          pos = lds_put_leb(L.img, pos, m.klen);
-          lds_copy(L.img, pos, L.keys, kst, m.klen, lane);
-        }
-      } else {
-        const uint32_t from = head ? 0 : m.sh;
-        if (part == 0) {  // header varints, key suffix, value length
-          L.img[pos++] = (uint8_t)m.vt;
-          pos = lds_put_leb(L.img, pos, m.seq);
-          if (!head) pos = lds_put_leb(L.img, pos, m.sh);
-          pos = lds_put_leb(L.img, pos, m.klen - from);
-          lds_copy(L.img, pos, L.keys, kst + from, m.klen - from, lane);
-          pos += m.klen - from;
-          if (!is_tombstone(m.vt)) pos = lds_put_leb(L.img, pos, m.vl);
-        }
-        if (!is_tombstone(m.vt)) {  // the value: part q copies bytes [q vl / tpi, (q + 1) vl / tpi)
-          uint32_t vpos = pos;
-          if (part != 0)
-            vpos = p0 + roff + 1 + leb_len(m.seq) + (head ? 0u : leb_len(m.sh)) + leb_len(m.klen - from) +
-                   (m.klen - from) + leb_len(m.vl);
-          const uint32_t va = (part * m.vl) >> tsh, vb = ((part + 1) * m.vl) >> tsh;
-          lds_copy(L.img, vpos + va, L.vals, (uint32_t)(m.vo - vbase) + va, vb - va, lane);
-        }
-      }
-      if (head && part == 0) {
-        const uint32_t bp = p0 + B.recs + 1 + (m.e >> 16) * B.step;
-        for (uint32_t q = 0; q < B.step; ++q) L.img[bp + q] = (uint8_t)(roff >> (8 * q));
-      }
-      if (kHash && B.hash_w && part == 0) {
         const uint32_t ridx = (item - B.it0) / ri;
         const uint32_t hb =
             kPlanBkt ? m.hb
@@ -2252,7 +2290,34 @@ __global__ __launch_bounds__(kGThreads) __attribute__((amdgpu_waves_per_eu(4))) 
         atomicMin(&hlo[bk], ridx);
         atomicMax(&hhi[bk], ridx);
       }
-    }
+    };
+    constexpr bool uniform = !index;
+    if (tsh == 0) {
+      uint32_t vpos = 0;
+      if (writes) vpos = put_header();
+      const uint32_t done =
+          uniform ? lds_copy_uniform(L.img, vpos, L.vals, vsrc, m.vl, has_val && m.vl != 0, lane) : 0u;
+      if (writes) {
+        if (has_val) lds_copy(L.img, vpos, L.vals, vsrc, m.vl, lane, done);
+        put_index_and_vote();
+      }
+    } else {
+      // the value: part q copies bytes [q vl / tpi, (q + 1) vl / tpi)
+      const uint32_t va = (part * m.vl) >> tsh, vb = ((part + 1) * m.vl) >> tsh;
+      uint32_t vpos = 0;
+      if (writes) {
+        if (part == 0)
+          vpos = put_header();
+        else if (has_val)
+          vpos = TB[j].img + kHdrLen + roff + 1 + leb_len(m.seq) + (head ? 0u : leb_len(m.sh)) + leb_len(m.klen - from) +
+                 (m.klen - from) + leb_len(m.vl);
+      }
+      const uint32_t done =
+          uniform ? lds_copy_uniform(L.img, vpos + va, L.vals, vsrc + va, vb - va, has_val && vb != va, lane) : 0u;
+      if (writes) {
+        if (has_val) lds_copy(L.img, vpos + va, L.vals, vsrc + va, vb - va, lane, done);
+        if (part == 0) put_index_and_vote();
+      }
     }
     // ---- tails, wave per block: marker, hash-index bytes, trailer (trailer.rs:78-173);
     // without hash indexes they need nothing from the other waves' records

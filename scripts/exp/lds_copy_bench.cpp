@@ -7,6 +7,14 @@
 //   2 mskor      branch-free: every dest dword via ds_mskor_b32 (edges masked)
 //   3 ub128      unaligned ds_read_b128 / ds_write_b128 (4-byte aligned) + alignbyte
 //   4 plain      no rotation, linear 4-dword steps (conflicted source)
+//   9 uni-read2  the first B interior dwords (B = wave minimum, in an SGPR) in a loop
+//                with a uniform trip count: wrap as min(x, x - B), both source dwords of
+//                a destination dword by ds_read2_b32, no predicate; one dword more where
+//                the lane has it, the head and tail bytes by 0
+//  10 uni-carry  the same loop, each source dword read once (carried; a select at the wrap)
+//  11 uni-r2-u8  9 unrolled by 8
+// (9-11 as encode.hip's lds_copy_uniform: the last step of a B that is no multiple of the
+// unroll wraps on over dwords already copied instead of a remainder loop)
 // Each variant's image is checked against a host reference.
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -24,8 +32,10 @@ __device__ __forceinline__ void mskor(uint32_t addr, uint32_t mask, uint32_t dat
   asm volatile("ds_mskor_b32 %0, %1, %2" ::"v"(addr), "v"(mask), "v"(data) : "memory");
 }
 
+// `done`: interior dwords already copied (V == 0 only: the uniform variants' remainder)
 template <int V>
-__device__ __forceinline__ void copy(uint8_t* dst, uint32_t d, const uint8_t* src, uint32_t s, uint32_t n, uint32_t rot) {
+__device__ __forceinline__ void copy(uint8_t* dst, uint32_t d, const uint8_t* src, uint32_t s, uint32_t n, uint32_t rot,
+                                     uint32_t done = 0) {
   if (V == 0 || V == 1 || V == 4) {
     const uint32_t h = min(n, (4u - (d & 3u)) & 3u);
     uint32_t hb[3];
@@ -34,8 +44,8 @@ __device__ __forceinline__ void copy(uint8_t* dst, uint32_t d, const uint8_t* sr
 #pragma unroll
     for (uint32_t k = 0; k < 3; ++k) if (k < h) dst[d + k] = (uint8_t)hb[k];
     if (n == h) return;
-    const uint32_t d1 = d + h, e = d + n, body = ((e & ~3u) - d1) >> 2;
-    const uint32_t sp = s + h, sh = sp & 3u;
+    const uint32_t d1 = d + h + 4 * done, e = d + n, body = ((e & ~3u) - d1) >> 2;
+    const uint32_t sp = s + h + 4 * done, sh = sp & 3u;
     const uint32_t* s32 = reinterpret_cast<const uint32_t*>(src + (sp & ~3u));
     uint32_t* d32 = reinterpret_cast<uint32_t*>(dst + d1);
     if (V == 0) {
@@ -133,6 +143,73 @@ __device__ __forceinline__ void copy(uint8_t* dst, uint32_t d, const uint8_t* sr
   }
 }
 
+// wave-wide minimum into an SGPR (every lane active): four DPP steps inside the
+// 16-lane rows, then the four rows by v_readlane
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
+  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
+  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x141, 0xF, 0xF, false));  // row_half_mirror
+  v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x140, 0xF, 0xF, false));  // row_mirror
+  const uint32_t a = __builtin_amdgcn_readlane((int)v, 0), b = __builtin_amdgcn_readlane((int)v, 16);
+  const uint32_t c = __builtin_amdgcn_readlane((int)v, 32), e = __builtin_amdgcn_readlane((int)v, 48);
+  return min(min(a, b), min(c, e));
+}
+
+// The first B interior dwords of every lane's span (B wave-uniform, B >= 1): lane `rot`
+// starts at dword ((rot & 31) B) >> 5 and wraps modulo B.  kCarry: each source dword is
+// read once and carried to the next destination dword; else both come from one
+// ds_read2_b32.  Nothing in the body depends on the lane but addresses and data.
+// B >= U; the last step of a B that is no multiple of U stores some dwords twice.
+template <bool kCarry, uint32_t U>
+__device__ __forceinline__ void copy_interior(uint8_t* db, const uint8_t* sb, uint32_t sh, uint32_t B, uint32_t rot) {
+  auto ld = [&](uint32_t x) { return *reinterpret_cast<const uint32_t*>(sb + x); };
+  auto st = [&](uint32_t x, uint32_t v) { *reinterpret_cast<uint32_t*>(db + x) = v; };
+  const uint32_t B4 = 4 * B;
+  uint32_t x = (((rot & 31u) * B) >> 5) * 4;  // byte offset of the lane's next dword, < B4
+  const uint32_t w0 = kCarry ? ld(0) : 0;
+  uint32_t carry = kCarry ? ld(x) : 0;
+  for (uint32_t j = 0; j < B; j += U) {
+    uint32_t at[U], lo[U], hi[U];
+#pragma unroll
+    for (uint32_t t = 0; t < U; ++t) {
+      const uint32_t y = x + 4 * t;
+      at[t] = t == 0 ? x : min(y, y - B4);  // (y < B4: y - B4 wraps high)
+      if (!kCarry) lo[t] = ld(at[t]);
+      hi[t] = ld(at[t] + 4);
+    }
+#pragma unroll
+    for (uint32_t t = 0; t < U; ++t) {
+      if (kCarry) lo[t] = at[t] == 0 ? w0 : (t == 0 ? carry : hi[t - 1]);
+      st(at[t], ab(hi[t], lo[t], sh));
+    }
+    carry = hi[U - 1];
+    x += 4 * U;
+    x = min(x, x - B4);
+  }
+}
+
+// fewer uniform dwords than one step: the general loop alone
+template <bool kCarry, uint32_t U>
+__device__ __forceinline__ void copy_uniform(uint8_t* dst, uint32_t d, const uint8_t* src, uint32_t s, uint32_t n, uint32_t rot) {
+  const uint32_t h = min(n, (4u - (d & 3u)) & 3u);
+  const uint32_t body = n > h ? (((d + n) & ~3u) - (d + h)) >> 2 : 0u;
+  const uint32_t B = wave_min_u32(n ? body : 0xFFFFFFFFu);
+  uint32_t done = 0;
+  if (B >= U && B != 0xFFFFFFFFu) {
+    done = B;
+    if (n) {
+      const uint8_t* sb = src + ((s + h) & ~3u);
+      const uint32_t sh = (s + h) & 3u;
+      copy_interior<kCarry, U>(dst + d + h, sb, sh, B, rot);
+      if (body > B) {  // one dword more where the lane has it
+        *reinterpret_cast<uint32_t*>(dst + d + h + 4 * B) =
+            ab(*reinterpret_cast<const uint32_t*>(sb + 4 * B + 4), *reinterpret_cast<const uint32_t*>(sb + 4 * B), sh);
+        done = B + 1;
+      }
+    }
+  }
+  copy<0>(dst, d, src, s, n, rot, done);
+}
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef const __attribute__((address_space(1))) void gbl_void_t;
@@ -253,7 +330,10 @@ __global__ __launch_bounds__(kWG) void bench(const uint8_t* vals, const uint32_t
   __syncthreads();
   const uint32_t d = dpos[t];
   for (int it = 0; it < iters; ++it) {
-    copy<V>(img, d, stage, kVal * t, kVal, t & 63);
+    if (V == 9) copy_uniform<false, 4>(img, d, stage, kVal * t, kVal, t & 63);
+    else if (V == 10) copy_uniform<true, 4>(img, d, stage, kVal * t, kVal, t & 63);
+    else if (V == 11) copy_uniform<false, 8>(img, d, stage, kVal * t, kVal, t & 63);
+    else copy<V>(img, d, stage, kVal * t, kVal, t & 63);
     __builtin_amdgcn_s_waitcnt(0xc07f);
     __builtin_amdgcn_s_barrier();
   }
@@ -360,5 +440,12 @@ int main() {
   run("8 rows", bench_row<8>);
   run("0 rot-wrap", bench<0>);
   run("8 rows", bench_row<8>);
+  // the uniform-interior loops against 0, three repeats each (the spread of 0 is the noise)
+  for (int r = 0; r < 3; ++r) {
+    run("0 rot-wrap", bench<0>);
+    run("9 uni-read2", bench<9>);
+    run("10 uni-carry", bench<10>);
+    run("11 uni-r2-u8", bench<11>);
+  }
   return 0;
 }
