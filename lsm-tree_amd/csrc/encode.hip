@@ -1416,6 +1416,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void e
 //   out    16 B/lane copy of the group's span: the header-free pieces by three waves
 //          while the fourth runs the chains, then the header pieces
 // Blocks that do not fit are written by the list / HBM kernels.
+// Runs of small data blocks (no hash index, no fused plan) are written wave per block
+// instead, without the groups and their barriers: WaveSlot below and the loop in the kernel.
 struct GBlk {
   uint32_t it0, n;         // first item (group-relative), items
   uint32_t img, plen;      // header position in the image, payload length
@@ -1426,12 +1428,44 @@ struct GBlk {
 };
 static_assert(sizeof(GBlk) == 48, "GBlk");
 
+// The wave-per-block loop of the group kernel (data blocks without a hash index or the
+// fused plan): each wave of the workgroup has a stage and an image of its own, over the
+// group loop's LDS (the secret lies past them).  A 4 KiB block of 52 items, 16 B keys
+// and 64 B values (832 B of keys, 3328 B of values, 3.8 KB encoded) fits, and so does the
+// random-key 4 KiB class (4466 B blocks); four slots and the secret stay within the
+// 40,960 B that keep four workgroups on a CU.
+#ifdef LSM_NO_WAVE_BLOCKS
+constexpr bool kWaveBlocks = false;  // (A/B build: the group loop alone)
+#else
+constexpr bool kWaveBlocks = true;
+#endif
+constexpr uint32_t kWKeys = 1024, kWVals = 4096, kWImg = 4496;  // per-wave stage and image, as kGKeys / kGVals / kGImg
+constexpr uint32_t kWItems = kWave;                              // one lane per item
+constexpr uint32_t kWUnits = 5;                                  // hash units of an image, at most
+static_assert((kWImg - 1) / 1024 <= 4 && (kWImg - 1) / 1024 + 1 <= kWUnits,
+              "full KiB units and the tail unit of a payload");
+// diagnostic builds: lsm_block_params.reserved bit 0x20 makes every run take the group loop (the u8 has no
+// unused bit; this one is otherwise read only by the fused instantiation's look-back, which has no wave loop)
+constexpr uint32_t kDiagNoWaveBlocks = 0x20;
+struct WaveSlot {
+  uint8_t keys[kWKeys + kGSlack];
+  uint8_t vals[kWVals + kGSlack];
+  uint8_t img[kWImg + kGSlack];
+  uint64_t contrib[kWUnits * 8];
+};
+static_assert(offsetof(WaveSlot, vals) % 16 == 0 && offsetof(WaveSlot, img) % 16 == 0 && sizeof(WaveSlot) % 16 == 0,
+              "stage DMA and 16-B copy-out alignment");
+constexpr uint32_t kGroupBody = kGKeys + kGVals + kGImg + 3 * kGSlack + kGUnion + 2 * kGBlocks * (uint32_t)sizeof(GBlk);
+constexpr uint32_t kWaveSlots = kGWaves * (uint32_t)sizeof(WaveSlot);
+constexpr uint32_t kWavePad = kWaveSlots > kGroupBody ? kWaveSlots - kGroupBody : 16;
+
 struct GroupLds {
   uint8_t keys[kGKeys + kGSlack];
   uint8_t vals[kGVals + kGSlack];
   uint8_t img[kGImg + kGSlack];
   uint32_t uni[kGUnion / 4];
   GBlk blk[2][kGBlocks];  // this group's block table and the next one's (built under the chain)
+  uint8_t wave_pad[kWavePad];  // (the wave-per-block loop's slots, which lie over all of the above, end here)
   LongSecret secret;
 };
 // (the fused kernel's run-level plan keeps its LDS over vals + img, and its per-block
@@ -1439,6 +1473,13 @@ struct GroupLds {
 static_assert(offsetof(GroupLds, uni) - offsetof(GroupLds, vals) >= sizeof(PlanWaveLds), "plan LDS over the stage");
 static_assert(offsetof(GroupLds, vals) % 16 == 0, "plan LDS alignment");
 static_assert(kGRunFused * (sizeof(BlockPlan) + 8) + 16 <= kGUnion, "fused plan outputs in uni");
+static_assert(offsetof(GroupLds, wave_pad) == kGroupBody, "GroupLds layout");
+static_assert(kGWaves * sizeof(WaveSlot) <= offsetof(GroupLds, secret), "the wave slots lie over the group loop's LDS");
+static_assert(sizeof(GroupLds) <= 40960, "four workgroups per CU");
+
+__device__ __host__ __forceinline__ bool wave_fits(uint64_t n, uint64_t kspan, uint64_t vspan, uint64_t total) {
+  return n >= 1 && n <= kWItems && kspan + 15 <= kWKeys && vspan + 15 <= kWVals && total + 15 <= kWImg;
+}
 
 
 // n bytes src[s ..) (LDS) -> dst[d ..) (LDS): byte stores for the dst bytes
@@ -1587,6 +1628,38 @@ __device__ __forceinline__ uint32_t lds_put_leb(uint8_t* dst, uint32_t pos, uint
   }
   dst[pos++] = (uint8_t)v;
   return pos;
+}
+
+// A record up to its value, into the LDS image at `pos` (both loops of the group kernel):
+// type byte, varints, key (suffix from byte `from`; the key starts at keys[kst]), value
+// length.  Returns the value's place.
+template <bool kIndex>
+__device__ __forceinline__ uint32_t put_record_header(uint8_t* img, uint32_t pos, const uint8_t* keys, uint32_t kst,
+                                                      const ItemMeta& m, bool head, uint32_t from, uint32_t rot) {
+  if (kIndex) {
+    img[pos++] = 0;
+    pos = lds_put_leb(img, pos, m.vo);
+    pos = lds_put_leb(img, pos, m.vl);
+    pos = lds_put_leb(img, pos, m.seq);
+    pos = lds_put_leb(img, pos, m.klen);
+    lds_copy(img, pos, keys, kst, m.klen, rot);
+  } else {
+    img[pos++] = (uint8_t)m.vt;
+    pos = lds_put_leb(img, pos, m.seq);
+    if (!head) pos = lds_put_leb(img, pos, m.sh);
+    pos = lds_put_leb(img, pos, m.klen - from);
+    lds_copy(img, pos, keys, kst + from, m.klen - from, rot);
+    pos += m.klen - from;
+    if (!is_tombstone(m.vt)) pos = lds_put_leb(img, pos, m.vl);
+  }
+  return pos;
+}
+
+// A restart head's binary-index entry: its record offset, `step` bytes little-endian.
+// (`step` by reference: the group loop hands in its block table's word in LDS, read as
+// before between the byte stores; by value that loop took 6 VGPRs more in every instantiation)
+__device__ __forceinline__ void put_bin_entry(uint8_t* img, uint32_t bp, const uint32_t& step, uint32_t roff) {
+  for (uint32_t q = 0; q < step; ++q) img[bp + q] = (uint8_t)(roff >> (8 * q));
 }
 
 __device__ __forceinline__ void group_barrier() {
@@ -2188,6 +2261,197 @@ __global__ __launch_bounds__(kGThreads) __attribute__((amdgpu_waves_per_eu(4))) 
     }
   };
 
+  // ---- The wave-per-block loop.  A run whose every block is group-class, has at most
+  // kWItems items, fits a wave slot (wave_fits) and ends at or before out_cap is written
+  // wave per block: wave w takes blocks w, w + 4, ... of the run, lane = item, the four DPP
+  // rows of the wave hash the payload's 1 KiB units, a lane quad runs the scramble chain
+  // and writes the header, and the wave copies its block out.  Any other run (listed, bad,
+  // oversize or overflowing blocks, mixed batches) takes the group loop below, untouched.
+  // The choice is a ballot over the run registers, which every wave holds alike, so it is
+  // uniform over the workgroup.
+  // SYNCHRONISATION: the loop has no s_barrier, no __syncthreads() and no wait on another
+  // wave or workgroup; the waves' trip counts differ, so a barrier in it would hang.  The
+  // only barrier is the one below, before the loop, after the secret is copied to LDS.
+  // Within a wave, LDS writes and reads of different lanes are ordered by wave_lds_wait()
+  // (s_waitcnt lgkmcnt(0)), and the stage DMA by an explicit vmcnt(0).
+  constexpr bool kWaveLoop = kWaveBlocks && !kIndex && !kHash && !kPlanBkt && !kFused;
+  if constexpr (kWaveLoop) {
+    bool wave_run;
+    {
+      const uint32_t s1 = lane_u32(r_start, lane + 1);
+      const uint64_t o1 = lane_u64(r_off, lane + 1), k1 = lane_u64(r_ks, lane + 1), v1 = lane_u64(r_vs, lane + 1);
+      const bool fit = (r_plan.step_flags >> 8) == 0 && o1 <= P.out_cap &&
+                       wave_fits(s1 - r_start, k1 - (r_ks & ~15ULL), v1 - (r_vs & ~15ULL), o1 - (r_off & ~15ULL));
+      wave_run = __ballot(rb < b_end && !fit) == 0 && !(kDiagBuild && (P.diag & (kDiagNoWaveBlocks | 0x9F)));
+    }
+    if (wave_run) {
+      WaveSlot& W = reinterpret_cast<WaveSlot*>(&L)[wave];
+      auto wave_lds_wait = [&]() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); };
+      auto wave_dma = [&](uint32_t r) {
+        const uint64_t ka = rl64(r_ks, r) & ~15ULL, kb = rl64(r_ks, r + 1);
+        const uint64_t va = rl64(r_vs, r) & ~15ULL, vb = rl64(r_vs, r + 1);
+        const uint32_t kc = (uint32_t)((kb - ka + 15) >> 4), vc = (uint32_t)((vb - va + 15) >> 4);
+        const uint8_t* ks = P.it.keys + ka + 16 * lane;
+        for (uint32_t i = 0; i * kWave < kc; ++i)
+          if (i * kWave + lane < kc)
+            __builtin_amdgcn_global_load_lds((gbl_void_t*)(ks + 1024 * i), (lds_void_t*)(W.keys + 1024 * i), 16, 0, 0);
+        const uint8_t* vs = P.it.vals + va + 16 * lane;
+        for (uint32_t i = 0; i * kWave < vc; ++i)
+          if (i * kWave + lane < vc)
+            __builtin_amdgcn_global_load_lds((gbl_void_t*)(vs + 1024 * i), (lds_void_t*)(W.vals + 1024 * i), 16, 0, 0);
+      };
+      auto wave_items = [&](uint32_t r, RawItemT<kOW, kIndex>& x) {
+        const uint32_t i0 = rl32(r_start, r), n = rl32(r_start, r + 1) - i0;
+        const uint64_t i = (uint64_t)i0 + min((uint32_t)lane, n - 1);
+        x = load_raw<kIndex, kOW>(P, i);
+        x.e = P.erec[i];
+      };
+      group_barrier_lds();  // the secret is in LDS; the last barrier of this run
+      uint32_t r = wave;
+      const uint32_t nr = b_end - b_begin;
+      RawItemT<kOW, kIndex> raw{};
+      if (r < nr) {
+        wave_dma(r);
+        wave_items(r, raw);
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      while (r < nr) {
+        const uint32_t i0 = rl32(r_start, r), n = rl32(r_start, r + 1) - i0;
+        const uint64_t kbase = rl64(r_ks, r) & ~15ULL, vbase = rl64(r_vs, r) & ~15ULL;
+        const uint64_t obase = rl64(r_off, r);
+        const uint32_t total = (uint32_t)(rl64(r_off, r + 1) - obase), plen = total - kHdrLen;
+        const uint32_t recs = rl32(r_plan.recs, r), bin_len = rl32(r_plan.bin_len, r);
+        const uint32_t step = rl32(r_plan.step_flags, r) & 0xFF;
+        const uint64_t dabs = (uint64_t)(uintptr_t)P.out + obase;
+        const uint32_t pad = (uint32_t)(dabs & 15), p0 = pad + kHdrLen;
+        const uint32_t rn = r + kGWaves;
+        const bool more = rn < nr;
+        // the next block's item fields: in flight under this whole block
+        ItemMeta m = cook(raw);
+        if (more) wave_items(rn, raw);
+        // ---- lane = item: its record into the image (the group loop's one-thread writer)
+        {
+          const bool live = (uint32_t)lane < n;
+          const bool head = (m.e & kErecHead) != 0;
+          m.sh = head ? 0u : m.e >> 16;
+          const uint32_t roff = m.e & 0x7FFFu, from = head ? 0 : m.sh;
+          const uint32_t kst = (uint32_t)(m.ko - kbase), vsrc = (uint32_t)(m.vo - vbase);
+          const bool has_val = live && !is_tombstone(m.vt);
+          uint32_t vpos = 0;
+          if (live) vpos = put_record_header<false>(W.img, p0 + roff, W.keys, kst, m, head, from, lane);
+          const uint32_t done = lds_copy_uniform(W.img, vpos, W.vals, vsrc, m.vl, has_val && m.vl != 0, lane);
+          if (live) {
+            if (has_val) lds_copy(W.img, vpos, W.vals, vsrc, m.vl, lane, done);
+            if (head) put_bin_entry(W.img, p0 + recs + 1 + (m.e >> 16) * step, step, roff);
+          }
+        }
+        // ---- marker and trailer
+        if (lane == 0) W.img[p0 + recs] = kTrailerMarker;
+        write_trailer_bytes(W.img, p0 + plen - kTrailerLen, ri, step, bin_len, recs + 1, 0, 0, n);
+        wave_lds_wait();
+        // the stage is free: the next block's DMA runs under the hash, the chain and the copy-out
+        if (more) wave_dma(rn);
+        // ---- payload xxh3_128: the wave's four DPP rows take the 1 KiB units
+        uint64_t lo = 0, hi = 0;
+        const int q = lane & 3;
+        if (plen > 240) {
+          const uint32_t nbk = (plen - 1) / 1024;
+          {
+            const uint32_t row = (uint32_t)lane >> 4, rr = lane & 15, s = rr >> 2;
+            const uint64_t* acc = L.secret.acc + s + 2 * q;
+            for (uint32_t u = row; u <= nbk; u += 4) {
+              uint64_t c0 = 0, c1 = 0;
+              if (u < nbk) {
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                  const Win16 w = read_win16(W.img, p0 + u * 1024 + 256 * t + 16 * rr);
+                  stripe_part(w, acc[4 * t], acc[4 * t + 1], c0, c1);
+                }
+              } else {  // the tail stripes and the last stripe (secret + 121)
+                const uint32_t tail0 = nbk * 1024, nb_stripes = ((plen - 1) - tail0) / 64;
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                  if ((uint32_t)(4 * t + s) < nb_stripes) {
+                    const Win16 w = read_win16(W.img, p0 + tail0 + 256 * t + 16 * rr);
+                    stripe_part(w, acc[4 * t], acc[4 * t + 1], c0, c1);
+                  }
+                }
+                if (rr < 4) {
+                  const Win16 w = read_win16(W.img, p0 + plen - 64 + 16 * rr);
+                  stripe_part(w, L.secret.last[2 * q], L.secret.last[2 * q + 1], c0, c1);
+                }
+              }
+              c0 = row_quad_sum64(c0);
+              c1 = row_quad_sum64(c1);
+              if (rr < 4) {
+                W.contrib[8 * u + 2 * q] = c0;
+                W.contrib[8 * u + 2 * q + 1] = c1;
+              }
+            }
+          }
+          wave_lds_wait();
+          // ---- the scramble chain and the merge: every quad computes the same (lane q holds
+          // accumulator pair q; the reads are LDS broadcasts), quad 0 writes the header
+          uint64_t a0 = q == 0 ? (uint64_t)P32_3 : q == 1 ? P64_2 : q == 2 ? P64_4 : P64_5;
+          uint64_t a1 = q == 0 ? P64_1 : q == 1 ? P64_3 : q == 2 ? (uint64_t)P32_2 : (uint64_t)P32_1;
+          const uint64_t scr0 = L.secret.acc[16 + 2 * q], scr1 = L.secret.acc[16 + 2 * q + 1];
+          const uint64_t* cb = W.contrib + 2 * q;
+          uint64_t c0[4], c1[4];  // (nbk <= 4; past the block's units: unused words of the buffer)
+#pragma unroll
+          for (uint32_t t = 0; t < 4; ++t) {
+            c0[t] = cb[8 * t];
+            c1[t] = cb[8 * t + 1];
+          }
+          const uint64_t t0 = cb[8 * nbk], t1 = cb[8 * nbk + 1];
+#pragma unroll
+          for (uint32_t t = 0; t < 4; ++t) {
+            if (t < nbk) {
+              a0 = xxh3_scr(a0, c0[t], scr0);
+              a1 = xxh3_scr(a1, c1[t], scr1);
+            }
+          }
+          a0 += t0;
+          a1 += t1;
+          lo = mul_fold64(a0 ^ L.secret.mlo[2 * q], a1 ^ L.secret.mlo[2 * q + 1]);
+          hi = mul_fold64(a0 ^ L.secret.mhi[2 * q], a1 ^ L.secret.mhi[2 * q + 1]);
+        }
+        lo = quad_sum64(lo);  // (every lane: DPP reads of inactive lanes are undefined)
+        hi = quad_sum64(hi);
+        if (lane < 4) {
+          if (plen > 240) {
+            lo = xxh3_avalanche((uint64_t)plen * P64_1 + lo);
+            hi = xxh3_avalanche(~((uint64_t)plen * P64_2) + hi);
+          } else {
+            xxh3_128_short(plen, BaseReader8{W.img, p0}, BaseReader64{W.img, p0}, lo, hi);
+          }
+          write_header_quad(W.img, pad, P.type, lo, hi, plen, q);
+          if (lane == 0) P.status[b_begin + r] = ST_OK;
+        }
+        wave_lds_wait();
+        // the next block's DMA pieces and item fields, before this block's stores are
+        // issued: the stores never count in this wait
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // ---- copy-out: the whole 16-B pieces [c0, c1), then the partial pieces at the
+        // block's two ends with one masked byte store each (lane x stores byte x; the
+        // rest of those pieces belongs to the neighbouring blocks)
+        {
+          const uint32_t end = pad + total, c0 = (pad + 15) >> 4, c1 = end >> 4;
+          const u32x4* const csrc = reinterpret_cast<const u32x4*>(W.img);
+          u32x4* const cdst = reinterpret_cast<u32x4*>(dabs & ~15ULL);
+          for (uint32_t c = c0 + (uint32_t)lane; c < c1; c += kWave)
+            *(__attribute__((address_space(1))) u32x4*)(cdst + c) = csrc[c];
+          auto* gb = (__attribute__((address_space(1))) uint8_t*)cdst;
+          const uint32_t x = (uint32_t)lane;
+          if (x >= pad && x < min(16 * c0, end)) gb[x] = W.img[x];
+          if (c1 >= c0 && 16 * c1 + x < end) gb[16 * c1 + x] = W.img[16 * c1 + x];
+        }
+        wave_lds_wait();  // (the image is read out before the next block's records are written)
+        r = rn;
+      }
+      return;
+    }
+  }
+
   // Software pipeline: group G's stage DMA and item fields are issued one
   // group ahead and waited for (vmcnt(0)) just before the previous group's
   // copy-out, so no group waits on HBM latency after its stores.
@@ -2256,31 +2520,11 @@ __global__ __launch_bounds__(kGThreads) __attribute__((amdgpu_waves_per_eu(4))) 
     const uint32_t vsrc = (uint32_t)(m.vo - vbase);
     // type byte, varints, key (suffix), value length: up to the value, whose place it returns
     auto put_header = [&]() -> uint32_t {
-      uint32_t pos = TB[j].img + kHdrLen + roff;
-      if (index) {
-        L.img[pos++] = 0;
-        pos = lds_put_leb(L.img, pos, m.vo);
-        pos = lds_put_leb(L.img, pos, m.vl);
-        pos = lds_put_leb(L.img, pos, m.seq);
-        pos = lds_put_leb(L.img, pos, m.klen);
-        lds_copy(L.img, pos, L.keys, kst, m.klen, lane);
-      } else {
-        L.img[pos++] = (uint8_t)m.vt;
-        pos = lds_put_leb(L.img, pos, m.seq);
-        if (!head) pos = lds_put_leb(L.img, pos, m.sh);
-        pos = lds_put_leb(L.img, pos, m.klen - from);
-        lds_copy(L.img, pos, L.keys, kst + from, m.klen - from, lane);
-        pos += m.klen - from;
-        if (!is_tombstone(m.vt)) pos = lds_put_leb(L.img, pos, m.vl);
-      }
-      return pos;
+      return put_record_header<index>(L.img, TB[j].img + kHdrLen + roff, L.keys, kst, m, head, from, lane);
     };
     auto put_index_and_vote = [&]() {
       const GBlk& B = TB[j];
-      if (head) {
-        const uint32_t bp = B.img + kHdrLen + B.recs + 1 + (m.e >> 16) * B.step;
-        for (uint32_t q = 0; q < B.step; ++q) L.img[bp + q] = (uint8_t)(roff >> (8 * q));
-      }
+      if (head) put_bin_entry(L.img, B.img + kHdrLen + B.recs + 1 + (m.e >> 16) * B.step, B.step, roff);
       if (kHash && B.hash_w) {
         const uint32_t ridx = (item - B.it0) / ri;
         const uint32_t hb =
