@@ -145,14 +145,6 @@ __device__ __forceinline__ RecHead rec_head(uint64_t h, bool restart) {
   r.q = r.hdr + r.klen;  // <= 136
   return r;
 }
-// two bytes at offset q (q <= 14) of the window, branch-free
-__device__ __forceinline__ uint32_t win16_u16(const Win16& w, uint32_t q) {
-  const uint32_t d0 = (uint32_t)w.lo, d1 = (uint32_t)(w.lo >> 32), d2 = (uint32_t)w.hi, d3 = (uint32_t)(w.hi >> 32);
-  const uint32_t qi = q >> 2;
-  const uint32_t lo = qi == 0 ? d0 : qi == 1 ? d1 : qi == 2 ? d2 : d3;
-  const uint32_t hi = qi == 0 ? d1 : qi == 1 ? d2 : qi == 2 ? d3 : 0u;
-  return alignbyte(hi, lo, q & 3) & 0xFFFF;
-}
 // value length from the two bytes at start + q; false = longer varint
 __device__ __forceinline__ bool rec_vlen(uint32_t z, bool tomb, uint32_t& n4, uint32_t& vl) {
   const bool two = (z & 0x80) != 0;

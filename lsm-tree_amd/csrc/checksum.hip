@@ -1,6 +1,6 @@
 // checksum.hip — batched xxh3_128 (hash128, src/hash.rs:7-9) of arbitrary
 // byte ranges in HBM: one wave per range, the wave-cooperative long path from
-// device_common.hpp.  Used by tests to pin the device XXH3 against
+// xxh3.hpp.  Used by tests to pin the device XXH3 against
 // python-xxhash / the reference KATs, and available to callers that checksum
 // ranges themselves (e.g. Block::write_into of externally built payloads).
 #include <hip/hip_runtime.h>
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(512) void xxh3_stream_buffer_kernel(Xxh3Stream* __r
 // merge and the avalanche.  One wave; the state is not modified.
 __device__ __forceinline__ void stream_digest_wave(const Xxh3Stream* __restrict__ st, uint64_t* __restrict__ out) {
   const int lane = threadIdx.x & 63;
-  const int q = lane & 3, s = lane >> 2;
+  const int q = lane & 3;
   const LongSecret* ls = &kLongSecret;
   const uint8_t* sb = reinterpret_cast<const uint8_t*>(st);
   const uint64_t len = st->total;
@@ -208,22 +208,12 @@ __device__ __forceinline__ void stream_digest_wave(const Xxh3Stream* __restrict_
   if (len <= 240) {  // short paths: every byte is still pending
     xxh3_128_wave(sb, buf, (uint32_t)len, ls, lo, hi);
   } else {
+    // pend is in 1..1024 here (stream_buffer_wg, the only writer once total > 0, leaves
+    // t - 1024 ((t - 1) / 1024) bytes pending): the pending bytes are all tail, and the
+    // last stripe's 64 bytes before buf + pend are in hist || buf
     uint64_t a0 = st->acc[2 * q], a1 = st->acc[2 * q + 1];
-    const uint32_t nb_stripes = (pend - 1) / 64;
-    uint64_t c0 = 0, c1 = 0;
-    if ((uint32_t)s < nb_stripes)
-      stripe_part(read_win16(sb, buf + 16 * lane), ls->acc[s + 2 * q], ls->acc[s + 2 * q + 1], c0, c1);
-    if (lane < 4) stripe_part(read_win16(sb, buf + pend - 64 + 16 * lane), ls->last[2 * q], ls->last[2 * q + 1], c0, c1);
-    a0 += quad_group_sum64(c0);
-    a1 += quad_group_sum64(c1);
-    uint64_t tlo = mul_fold64(a0 ^ ls->mlo[2 * q], a1 ^ ls->mlo[2 * q + 1]);
-    uint64_t thi = mul_fold64(a0 ^ ls->mhi[2 * q], a1 ^ ls->mhi[2 * q + 1]);
-    tlo += shfl_xor64(tlo, 1);
-    thi += shfl_xor64(thi, 1);
-    tlo += shfl_xor64(tlo, 2);
-    thi += shfl_xor64(thi, 2);
-    lo = xxh3_avalanche(len * P64_1 + tlo);
-    hi = xxh3_avalanche(~(len * P64_2) + thi);
+    xxh3_tail_wave(sb, buf, pend, ls, a0, a1);
+    xxh3_merge_wave(ls, q, len, a0, a1, lo, hi);
   }
   if (lane == 0) {
     out[0] = lo;

@@ -549,9 +549,6 @@ __device__ __forceinline__ void decode_block_direct(const DecodeParams& P, uint3
   wave_sync();
 }
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef const __attribute__((address_space(1))) void gbl_void_t;
-
 // Blocks whose span exceeds this go to the big-block kernel: those larger
 // than the stage.  (Half the stage measured slower: the 17 KB blocks of the
 // 16 KiB random-key class run at 0.82 TB/s through the big-block kernel, one
@@ -675,13 +672,7 @@ __device__ __forceinline__ void decode_chunked(const DecodeParams& P, uint32_t b
   for (uint32_t cs = 0; cs < span; cs += kChunkBytes) {
     const uint32_t ce = min(cs + kChunkBytes, span);
     const uint32_t ss = min(ce + kChunkOverlap, span);  // staged: [cs, ss)
-    {
-      const uint32_t chunks = (ss - cs + 15) >> 4;
-      const uint8_t* src = gbase + cs + 16 * lane;
-      for (uint32_t c = wave; c * kWave < chunks; c += kBigWaves)
-        if (c * kWave + lane < chunks)
-          __builtin_amdgcn_global_load_lds((gbl_void_t*)(src + 1024 * c), (lds_void_t*)(stage + 1024 * c), 16, 0, 0);
-    }
+    stage_to_lds(gbase + cs, stage, (ss - cs + 15) >> 4, wave, kBigWaves, lane);
     vm_wait<0>();
     lds_barrier();
     const uint8_t* sbase = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(stage) - cs);  // span-relative
@@ -700,12 +691,8 @@ __device__ __forceinline__ void decode_chunked(const DecodeParams& P, uint32_t b
       s_cur = r < nint ? bin_get(gbase, p0, t, r) : 0xFFFFFFFFu;
     }
     lds_barrier();
-    if (wave == 0 && hash) {  // the chain over this chunk's KiB blocks, in order
-      for (uint32_t n = 0; n < n1 - n0; ++n) {
-        a0 = xxh3_scr(a0, contrib[8 * n + 2 * (lane & 3)], scr0);
-        a1 = xxh3_scr(a1, contrib[8 * n + 2 * (lane & 3) + 1], scr1);
-      }
-    }
+    // the chain over this chunk's KiB blocks, in order
+    if (wave == 0 && hash) xxh3_quad_chain<1>(contrib + 2 * (lane & 3), n1 - n0, scr0, scr1, a0, a1);
     lds_barrier();  // (the next chunk overwrites the stage and the contributions)
   }
   if (r < nint) ok = false;  // a record start beyond the block
@@ -755,15 +742,10 @@ __global__ __launch_bounds__(kBigWaves * kWave) void decode_deferred_staged_kern
       lds_barrier();
       continue;
     }
-    const uint32_t chunks = (uint32_t)((span1 - span0) >> 4);
-    const uint8_t* src = P.blocks + span0 + 16 * lane;
-    for (uint32_t c = wave; c * kWave < chunks; c += kBigWaves) {
-      if (c * kWave + lane < chunks)
-        __builtin_amdgcn_global_load_lds((gbl_void_t*)(src + 1024 * c), (lds_void_t*)(stage + 1024 * c), 16, 0, 0);
-    }
+    stage_to_lds(P.blocks + span0, stage, (uint32_t)((span1 - span0) >> 4), wave, kBigWaves, lane);
     const uint64_t item_base = gload(P.item_start, b);
     const uint32_t cap = gload(P.item_start, b + 1) - (uint32_t)item_base;
-    __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0): this wave's DMA has landed
+    vm_lgkm_wait0();  // this wave's DMA has landed
     lds_barrier();
     const uint32_t hb = (uint32_t)(off & 15);
     if (tid == 0) {
@@ -1144,11 +1126,7 @@ __global__ __launch_bounds__(kBigGWaves * kWave) void decode_big_kernel(DecodePa
     }
   };
   auto issue_dma = [&](const BigBlk& x, uint8_t* dst) {  // wave w moves 1-KiB pieces w, w + 8, ...
-    const uint32_t chunks = (uint32_t)((x.span1 - x.span0) >> 4);
-    const uint8_t* src = P.blocks + x.span0 + 16 * lane;
-    for (uint32_t c = wave; c * kWave < chunks; c += kBigGWaves)
-      if (c * kWave + lane < chunks)
-        __builtin_amdgcn_global_load_lds((gbl_void_t*)(src + 1024 * c), (lds_void_t*)(dst + 1024 * c), 16, 0, 0);
+    stage_to_lds(P.blocks + x.span0, dst, (uint32_t)((x.span1 - x.span0) >> 4), wave, kBigGWaves, lane);
   };
   for (uint32_t x = tid; x < kBigGStage / 1024 + 1; x += kThreads) sync->ready[x] = 0;
   if (tid == 0) sync->a_done = 0;
@@ -1469,13 +1447,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void d
     const uint8_t* gbase = P.blocks + r->span0;
     const uint32_t cs = wc * kHugeWin;
     const uint32_t ce = min(cs + kHugeWin, span), ss = min(ce + kHugeOverlap, span);
-    {  // stage [cs, ss): wave w moves 1-KiB pieces w, w + 4, ...
-      const uint32_t chunks = (ss - cs + 15) >> 4;
-      const uint8_t* src = gbase + cs + 16 * lane;
-      for (uint32_t c = wave; c * kWave < chunks; c += 4)
-        if (c * kWave + lane < chunks)
-          __builtin_amdgcn_global_load_lds((gbl_void_t*)(src + 1024 * c), (lds_void_t*)(stage + 1024 * c), 16, 0, 0);
-    }
+    // stage [cs, ss): wave w moves 1-KiB pieces w, w + 4, ...
+    stage_to_lds(gbase + cs, stage, (ss - cs + 15) >> 4, wave, 4, lane);
     // the intervals that start in [cs, ce): [r0, r1), from the unit table, or (a binary index
     // that is not monotone) by a 256-way search of the binary index (HBM)
     const bool parse = m.st == ST_OK;
@@ -1761,11 +1734,7 @@ __global__ __launch_bounds__(kGroupWaves * kWave) __attribute__((amdgpu_waves_pe
   // LDS-DMA of a group's span (wave w moves 1-KiB pieces w, w + 4, ...).
   auto issue_dma = [&](const Group& g, uint8_t* dst) {
     const uint32_t chunks = (kDiagBuild && (P.flags & kDiagSkipDma)) ? 0u : (uint32_t)((g.span1 - g.span0) >> 4);
-    const uint8_t* src = P.blocks + g.span0 + 16 * lane;
-    for (uint32_t i = wave; i * kWave < chunks; i += kGroupWaves) {
-      if (i * kWave + lane < chunks)
-        __builtin_amdgcn_global_load_lds((gbl_void_t*)(src + 1024 * i), (lds_void_t*)(dst + 1024 * i), 16, 0, 0);
-    }
+    stage_to_lds(P.blocks + g.span0, dst, chunks, wave, kGroupWaves, lane);
   };
   // Lone blocks (larger than the stage, or more items than a tile) go to the
   // general path, decode_deferred_staged_kernel (a 72 KiB stage, the block

@@ -184,60 +184,6 @@ __device__ __forceinline__ uint64_t e2_need(uint64_t total, uint32_t hash_w) {
 }
 
 // ------------------------------------------------------- record assembly
-// Byte sink over a 4-aligned base: dword stores for bytes wholly inside the
-// caller's record, byte stores at the seams shared with neighbour records.
-struct ByteWriter {
-  uint8_t* dst;
-  uint32_t pos;
-  uint64_t acc;
-  uint32_t nacc;
-  __device__ __forceinline__ void init(uint8_t* d, uint32_t p) { dst = d; pos = p; acc = 0; nacc = 0; }
-  __device__ __forceinline__ void drain() {
-    while (nacc && (pos & 3)) {
-      dst[pos++] = (uint8_t)acc;
-      acc >>= 8;
-      --nacc;
-    }
-    if (nacc >= 4) {
-      *reinterpret_cast<uint32_t*>(dst + pos) = (uint32_t)acc;
-      acc >>= 32;
-      nacc -= 4;
-      pos += 4;
-    }
-  }
-  __device__ __forceinline__ void byte(uint32_t b) {
-    acc |= (uint64_t)(b & 0xFF) << (8 * nacc);
-    ++nacc;
-    if (nacc >= 4) drain();
-  }
-  __device__ __forceinline__ void word(uint32_t v, uint32_t n) {  // n in 1..4 low bytes of v
-    if (n < 4) v &= (1u << (8 * n)) - 1;
-    acc |= (uint64_t)v << (8 * nacc);
-    nacc += n;
-    if (nacc >= 4) drain();
-  }
-  __device__ __forceinline__ void leb(uint64_t v) {  // varint-rs write_*_varint
-    while (v >= 0x80) {
-      byte((uint32_t)(v & 0x7F) | 0x80);
-      v >>= 7;
-    }
-    byte((uint32_t)v);
-  }
-  // n bytes from src_base[src_pos ..) (4-aligned base, any src_pos)
-  __device__ __forceinline__ void copy(const uint8_t* src_base, uint32_t src_pos, uint32_t n) {
-    uint32_t k = 0;
-    for (; k + 4 <= n; k += 4) word(read_u32_unaligned(src_base, src_pos + k), 4);
-    if (k < n) word(read_u32_unaligned(src_base, src_pos + k), n - k);
-  }
-  __device__ __forceinline__ void finish() {
-    while (nacc) {
-      dst[pos++] = (uint8_t)acc;
-      acc >>= 8;
-      --nacc;
-    }
-  }
-};
-
 // Destination pointers of the record writers: LDS images (lds8_t) or HBM
 // (gbl8_t), explicit so that the stores compile to ds_write / global_store
 // (a generic pointer gives flat stores, which also count on lgkmcnt: every
@@ -811,11 +757,7 @@ __device__ __forceinline__ void write_block_lds_mw(const EncodeParams& P, uint32
       const uint32_t n1 = min(nbk, n0 + 64);
       xxh3_kib_contribs(img, p0 + 1024 * n0, (n1 - n0) * 1024 + 1, &kLongSecret, contrib, wave, kLW);
       __syncthreads();
-      if (wave == 0)
-        for (uint32_t k = 0; k < n1 - n0; ++k) {
-          a0 = xxh3_scr(a0, contrib[8 * k + 2 * q], scr0);
-          a1 = xxh3_scr(a1, contrib[8 * k + 2 * q + 1], scr1);
-        }
+      if (wave == 0) xxh3_quad_chain<1>(contrib + 2 * q, n1 - n0, scr0, scr1, a0, a1);
       __syncthreads();
     }
     if (wave == 0) xxh3_wave_tail_merge(img, p0, plen, &kLongSecret, a0, a1, lo, hi);
@@ -2073,8 +2015,6 @@ template <bool kIndex, bool kHash, bool kPlanBkt, int kOW, bool kFused = false>
 __global__ __launch_bounds__(kGThreads) __attribute__((amdgpu_waves_per_eu(4))) void encode_group_kernel(EncodeParams P) {
   static_assert(!kFused || (!kIndex && !kHash), "the fused plan is for data blocks without a hash index");
   __shared__ GroupLds L;
-  typedef __attribute__((address_space(3))) void lds_void_t;
-  typedef const __attribute__((address_space(1))) void gbl_void_t;
   const uint32_t tid = threadIdx.x;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(tid / kWave);
   const int lane = tid & (kWave - 1);
@@ -2192,14 +2132,8 @@ __global__ __launch_bounds__(kGThreads) __attribute__((amdgpu_waves_per_eu(4))) 
     const uint64_t ka = rl64(r_ks, r0) & ~15ULL, kb = rl64(r_ks, r0 + g.k);
     const uint64_t va = rl64(r_vs, r0) & ~15ULL, vb = rl64(r_vs, r0 + g.k);
     const uint32_t kc = (uint32_t)((kb - ka + 15) >> 4), vc = index ? 0 : (uint32_t)((vb - va + 15) >> 4);
-    const uint8_t* ks = P.it.keys + ka + 16 * lane;
-    for (uint32_t i = wave; i * kWave < kc; i += kGWaves)
-      if (i * kWave + lane < kc)
-        __builtin_amdgcn_global_load_lds((gbl_void_t*)(ks + 1024 * i), (lds_void_t*)(L.keys + 1024 * i), 16, 0, 0);
-    const uint8_t* vs = P.it.vals + va + 16 * lane;
-    for (uint32_t i = wave; i * kWave < vc; i += kGWaves)
-      if (i * kWave + lane < vc)
-        __builtin_amdgcn_global_load_lds((gbl_void_t*)(vs + 1024 * i), (lds_void_t*)(L.vals + 1024 * i), 16, 0, 0);
+    stage_to_lds(P.it.keys + ka, L.keys, kc, wave, kGWaves, lane);
+    stage_to_lds(P.it.vals + va, L.vals, vc, wave, kGWaves, lane);
   };
   uint32_t* hlo = L.uni;                           // [kGHash] vote min
   uint32_t* hhi = hlo + kGHash;                    // [kGHash] vote max
@@ -2291,14 +2225,8 @@ __global__ __launch_bounds__(kGThreads) __attribute__((amdgpu_waves_per_eu(4))) 
         const uint64_t ka = rl64(r_ks, r) & ~15ULL, kb = rl64(r_ks, r + 1);
         const uint64_t va = rl64(r_vs, r) & ~15ULL, vb = rl64(r_vs, r + 1);
         const uint32_t kc = (uint32_t)((kb - ka + 15) >> 4), vc = (uint32_t)((vb - va + 15) >> 4);
-        const uint8_t* ks = P.it.keys + ka + 16 * lane;
-        for (uint32_t i = 0; i * kWave < kc; ++i)
-          if (i * kWave + lane < kc)
-            __builtin_amdgcn_global_load_lds((gbl_void_t*)(ks + 1024 * i), (lds_void_t*)(W.keys + 1024 * i), 16, 0, 0);
-        const uint8_t* vs = P.it.vals + va + 16 * lane;
-        for (uint32_t i = 0; i * kWave < vc; ++i)
-          if (i * kWave + lane < vc)
-            __builtin_amdgcn_global_load_lds((gbl_void_t*)(vs + 1024 * i), (lds_void_t*)(W.vals + 1024 * i), 16, 0, 0);
+        stage_to_lds(P.it.keys + ka, W.keys, kc, 0, 1, lane);
+        stage_to_lds(P.it.vals + va, W.vals, vc, 0, 1, lane);
       };
       auto wave_items = [&](uint32_t r, RawItemT<kOW, kIndex>& x) {
         const uint32_t i0 = rl32(r_start, r), n = rl32(r_start, r + 1) - i0;
@@ -2314,7 +2242,7 @@ __global__ __launch_bounds__(kGThreads) __attribute__((amdgpu_waves_per_eu(4))) 
         wave_dma(r);
         wave_items(r, raw);
       }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      vm_wait<0>();
       while (r < nr) {
         const uint32_t i0 = rl32(r_start, r), n = rl32(r_start, r + 1) - i0;
         const uint64_t kbase = rl64(r_ks, r) & ~15ULL, vbase = rl64(r_vs, r) & ~15ULL;
@@ -2357,32 +2285,10 @@ __global__ __launch_bounds__(kGThreads) __attribute__((amdgpu_waves_per_eu(4))) 
         if (plen > 240) {
           const uint32_t nbk = (plen - 1) / 1024;
           {
-            const uint32_t row = (uint32_t)lane >> 4, rr = lane & 15, s = rr >> 2;
-            const uint64_t* acc = L.secret.acc + s + 2 * q;
+            const uint32_t row = (uint32_t)lane >> 4, rr = lane & 15;
             for (uint32_t u = row; u <= nbk; u += 4) {
-              uint64_t c0 = 0, c1 = 0;
-              if (u < nbk) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                  const Win16 w = read_win16(W.img, p0 + u * 1024 + 256 * t + 16 * rr);
-                  stripe_part(w, acc[4 * t], acc[4 * t + 1], c0, c1);
-                }
-              } else {  // the tail stripes and the last stripe (secret + 121)
-                const uint32_t tail0 = nbk * 1024, nb_stripes = ((plen - 1) - tail0) / 64;
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                  if ((uint32_t)(4 * t + s) < nb_stripes) {
-                    const Win16 w = read_win16(W.img, p0 + tail0 + 256 * t + 16 * rr);
-                    stripe_part(w, acc[4 * t], acc[4 * t + 1], c0, c1);
-                  }
-                }
-                if (rr < 4) {
-                  const Win16 w = read_win16(W.img, p0 + plen - 64 + 16 * rr);
-                  stripe_part(w, L.secret.last[2 * q], L.secret.last[2 * q + 1], c0, c1);
-                }
-              }
-              c0 = row_quad_sum64(c0);
-              c1 = row_quad_sum64(c1);
+              uint64_t c0, c1;
+              xxh3_row_unit(W.img, p0, plen, nbk, u, rr, &L.secret, c0, c1);
               if (rr < 4) {
                 W.contrib[8 * u + 2 * q] = c0;
                 W.contrib[8 * u + 2 * q + 1] = c1;
@@ -2392,35 +2298,23 @@ __global__ __launch_bounds__(kGThreads) __attribute__((amdgpu_waves_per_eu(4))) 
           wave_lds_wait();
           // ---- the scramble chain and the merge: every quad computes the same (lane q holds
           // accumulator pair q; the reads are LDS broadcasts), quad 0 writes the header
-          uint64_t a0 = q == 0 ? (uint64_t)P32_3 : q == 1 ? P64_2 : q == 2 ? P64_4 : P64_5;
-          uint64_t a1 = q == 0 ? P64_1 : q == 1 ? P64_3 : q == 2 ? (uint64_t)P32_2 : (uint64_t)P32_1;
+          uint64_t a0, a1;
+          xxh3_acc_init(q, a0, a1);
           const uint64_t scr0 = L.secret.acc[16 + 2 * q], scr1 = L.secret.acc[16 + 2 * q + 1];
+          // one batch is the whole chain, and its read-ahead past the block's units stays in W.contrib
+          static_assert((kWImg - 1) / 1024 <= 4 && 4 <= kWUnits, "nbk <= 4");
           const uint64_t* cb = W.contrib + 2 * q;
-          uint64_t c0[4], c1[4];  // (nbk <= 4; past the block's units: unused words of the buffer)
-#pragma unroll
-          for (uint32_t t = 0; t < 4; ++t) {
-            c0[t] = cb[8 * t];
-            c1[t] = cb[8 * t + 1];
-          }
           const uint64_t t0 = cb[8 * nbk], t1 = cb[8 * nbk + 1];
-#pragma unroll
-          for (uint32_t t = 0; t < 4; ++t) {
-            if (t < nbk) {
-              a0 = xxh3_scr(a0, c0[t], scr0);
-              a1 = xxh3_scr(a1, c1[t], scr1);
-            }
-          }
+          xxh3_quad_chain_batch<4>(cb, 0, nbk, scr0, scr1, a0, a1);
           a0 += t0;
           a1 += t1;
-          lo = mul_fold64(a0 ^ L.secret.mlo[2 * q], a1 ^ L.secret.mlo[2 * q + 1]);
-          hi = mul_fold64(a0 ^ L.secret.mhi[2 * q], a1 ^ L.secret.mhi[2 * q + 1]);
+          xxh3_merge_part(&L.secret, q, a0, a1, lo, hi);
         }
         lo = quad_sum64(lo);  // (every lane: DPP reads of inactive lanes are undefined)
         hi = quad_sum64(hi);
         if (lane < 4) {
           if (plen > 240) {
-            lo = xxh3_avalanche((uint64_t)plen * P64_1 + lo);
-            hi = xxh3_avalanche(~((uint64_t)plen * P64_2) + hi);
+            xxh3_finish128(plen, lo, hi, lo, hi);
           } else {
             xxh3_128_short(plen, BaseReader8{W.img, p0}, BaseReader64{W.img, p0}, lo, hi);
           }
@@ -2430,7 +2324,7 @@ __global__ __launch_bounds__(kGThreads) __attribute__((amdgpu_waves_per_eu(4))) 
         wave_lds_wait();
         // the next block's DMA pieces and item fields, before this block's stores are
         // issued: the stores never count in this wait
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        vm_wait<0>();
         // ---- copy-out: the whole 16-B pieces [c0, c1), then the partial pieces at the
         // block's two ends with one masked byte store each (lane x stores byte x; the
         // rest of those pieces belongs to the neighbouring blocks)
@@ -2467,7 +2361,7 @@ __global__ __launch_bounds__(kGThreads) __attribute__((amdgpu_waves_per_eu(4))) 
     load_items(G, raw);
     if (wave == 0) build_table(G, L.blk[0]);  // (later tables are built under the previous chain)
   }
-  __builtin_amdgcn_s_waitcnt(0x0070);
+  vm_lgkm_wait0();  // the first group's DMA pieces and item fields
   ENC_PHASE(11);
   uint32_t iter = 0;  // rotates the chain wave over the SIMDs
   while (G.k) {
@@ -2592,38 +2486,15 @@ __global__ __launch_bounds__(kGThreads) __attribute__((amdgpu_waves_per_eu(4))) 
     ENC_PHASE(4);
     // ---- payload xxh3_128: 1 KiB units over the 16 DPP rows
     {
-      const uint32_t row = wave * 4 + (lane >> 4), r = lane & 15, q = r & 3, s = r >> 2;  // (4 kGWaves rows)
+      const uint32_t row = wave * 4 + (lane >> 4), r = lane & 15, q = r & 3;  // (4 kGWaves rows)
       const uint32_t ubase = rl32(r_upre, r0);
       const uint32_t units = (kDiagBuild && (P.diag & 10)) ? 0 : rl32(r_upre, r0 + k) - ubase;
-      const uint64_t* acc = L.secret.acc + s + 2 * q;
       for (uint32_t u = row; u < units; u += 4 * kGWaves) {
         uint32_t jb = 0;  // (unit starts from the run registers: no dependent LDS reads)
         for (uint32_t x = 1; x < k; ++x) jb += (rl32(r_upre, r0 + x) - ubase <= u) ? 1u : 0u;
         const GBlk& B = TB[jb];
-        const uint32_t n = u - B.u0, p0 = B.img + kHdrLen;
-        uint64_t c0 = 0, c1 = 0;
-        if (n < B.nbk) {
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            const Win16 w = read_win16(L.img, p0 + n * 1024 + 256 * t + 16 * r);
-            stripe_part(w, acc[4 * t], acc[4 * t + 1], c0, c1);
-          }
-        } else {  // the tail stripes and the last stripe (secret + 121)
-          const uint32_t tail0 = B.nbk * 1024, nb_stripes = ((B.plen - 1) - tail0) / 64;
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            if ((uint32_t)(4 * t + s) < nb_stripes) {
-              const Win16 w = read_win16(L.img, p0 + tail0 + 256 * t + 16 * r);
-              stripe_part(w, acc[4 * t], acc[4 * t + 1], c0, c1);
-            }
-          }
-          if (r < 4) {
-            const Win16 w = read_win16(L.img, p0 + B.plen - 64 + 16 * r);
-            stripe_part(w, L.secret.last[2 * q], L.secret.last[2 * q + 1], c0, c1);
-          }
-        }
-        c0 = row_quad_sum64(c0);
-        c1 = row_quad_sum64(c1);
+        uint64_t c0, c1;
+        xxh3_row_unit(L.img, B.img + kHdrLen, B.plen, B.nbk, u - B.u0, r, &L.secret, c0, c1);
         if (r < 4) {
           contrib[8 * u + 2 * q] = c0;
           contrib[8 * u + 2 * q + 1] = c1;
@@ -2657,38 +2528,21 @@ __global__ __launch_bounds__(kGThreads) __attribute__((amdgpu_waves_per_eu(4))) 
         const uint32_t p0 = B.img + kHdrLen, plen = B.plen;
         uint64_t lo = 0, hi = 0;
         if (in && plen > 240) {
-          uint64_t a0 = q == 0 ? (uint64_t)P32_3 : q == 1 ? P64_2 : q == 2 ? P64_4 : P64_5;
-          uint64_t a1 = q == 0 ? P64_1 : q == 1 ? P64_3 : q == 2 ? (uint64_t)P32_2 : (uint64_t)P32_1;
+          uint64_t a0, a1;
+          xxh3_acc_init(q, a0, a1);
           const uint64_t scr0 = L.secret.acc[16 + 2 * q], scr1 = L.secret.acc[16 + 2 * q + 1];
           const uint64_t* cb = contrib + 8 * B.u0 + 2 * q;
-          // four KiB blocks' contributions per batch, read without branches (past
-          // the block they read other contributions in L.uni, unused)
-          for (uint32_t n0 = 0; n0 < B.nbk; n0 += 4) {
-            uint64_t c0[4], c1[4];
-#pragma unroll
-            for (uint32_t t = 0; t < 4; ++t) {
-              c0[t] = cb[8 * (n0 + t)];
-              c1[t] = cb[8 * (n0 + t) + 1];
-            }
-#pragma unroll
-            for (uint32_t t = 0; t < 4; ++t) {
-              if (n0 + t < B.nbk) {
-                a0 = xxh3_scr(a0, c0[t], scr0);
-                a1 = xxh3_scr(a1, c1[t], scr1);
-              }
-            }
-          }
+          // (the batches' read-ahead past the block: other contributions in L.uni, unused)
+          xxh3_quad_chain<4>(cb, B.nbk, scr0, scr1, a0, a1);
           a0 += cb[8 * B.nbk];
           a1 += cb[8 * B.nbk + 1];
-          lo = mul_fold64(a0 ^ L.secret.mlo[2 * q], a1 ^ L.secret.mlo[2 * q + 1]);
-          hi = mul_fold64(a0 ^ L.secret.mhi[2 * q], a1 ^ L.secret.mhi[2 * q + 1]);
+          xxh3_merge_part(&L.secret, q, a0, a1, lo, hi);
         }
         lo = quad_sum64(lo);  // (every lane: DPP reads of inactive lanes are undefined)
         hi = quad_sum64(hi);
         if (in) {
           if (plen > 240) {
-            lo = xxh3_avalanche((uint64_t)plen * P64_1 + lo);
-            hi = xxh3_avalanche(~((uint64_t)plen * P64_2) + hi);
+            xxh3_finish128(plen, lo, hi, lo, hi);
           } else {
             xxh3_128_short(plen, BaseReader8{L.img, p0}, BaseReader64{L.img, p0}, lo, hi);
           }
@@ -2713,7 +2567,7 @@ __global__ __launch_bounds__(kGThreads) __attribute__((amdgpu_waves_per_eu(4))) 
     }
     group_barrier_lds();
     ENC_PHASE(6);
-    __builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0): the next group's DMA pieces and item fields
+    vm_lgkm_wait0();  // the next group's DMA pieces and item fields (vmcnt(0); the call waits on lgkmcnt as well)
     ENC_PHASE(7);
     // ---- copy-out, part 2: the header pieces and the partial pieces at both ends
     {
@@ -2869,11 +2723,7 @@ __global__ __launch_bounds__(kE3Threads) void encode_large_kernel(EncodeParams P
         const uint32_t n1 = min(nbk, n0 + 64);
         xxh3_kib_contribs<false>(img, p0 + 1024 * n0, (n1 - n0) * 1024 + 1, &kLongSecret, contrib, wave, kE3Waves);
         __syncthreads();
-        if (wave == 0)
-          for (uint32_t k = 0; k < n1 - n0; ++k) {
-            a0 = xxh3_scr(a0, contrib[8 * k + 2 * q], scr0);
-            a1 = xxh3_scr(a1, contrib[8 * k + 2 * q + 1], scr1);
-          }
+        if (wave == 0) xxh3_quad_chain<1>(contrib + 2 * q, n1 - n0, scr0, scr1, a0, a1);
         __syncthreads();
       }
       if (wave == 0) xxh3_wave_tail_merge(img, p0, plen, &kLongSecret, a0, a1, lo, hi);
