@@ -546,8 +546,11 @@ __device__ __forceinline__ void write_header_bytes(uint8_t* dst, uint32_t hp, ui
 
 // The same header written by a lane quad (lane q of the quad: bytes
 // [8q, 8q + 8), lane 0 also byte 32), every lane computing the 29-byte
-// checksum itself.
-__device__ __forceinline__ void write_header_quad(uint8_t* dst, uint32_t hp, uint32_t type, uint64_t ck_lo,
+// checksum itself.  BytePtr: uint8_t* (an LDS image, or any memory) or a global-
+// address-space byte pointer (the wave-per-block loop's deferred headers, which
+// go straight to the output).
+template <class BytePtr>
+__device__ __forceinline__ void write_header_quad(BytePtr dst, uint32_t hp, uint32_t type, uint64_t ck_lo,
                                                   uint64_t ck_hi, uint32_t plen, int q) {
   const uint64_t w0 = 0x034D534CULL | ((uint64_t)type << 32) | (ck_lo << 40);
   const uint64_t w1 = (ck_lo >> 24) | (ck_hi << 40);
@@ -1386,6 +1389,13 @@ constexpr uint32_t kWItems = kWave;                              // one lane per
 constexpr uint32_t kWUnits = 5;                                  // hash units of an image, at most
 static_assert((kWImg - 1) / 1024 <= 4 && (kWImg - 1) / 1024 + 1 <= kWUnits,
               "full KiB units and the tail unit of a payload");
+// Blocks of a wave whose scramble chains, checksum tails and headers are finished together, a
+// lane quad per block (flush_headers).  Every kept block costs two VGPRs (its contributions)
+// and two selects per block; 4 measured faster than 6 and 8, the wave's whole share of a
+// run.
+constexpr uint32_t kWDefer = 4;
+static_assert(kWDefer >= 1 && kWDefer <= kWave / 4, "one lane quad per deferred block");
+static_assert(kWDefer * kWUnits * 8 * 8 <= kWImg, "the kept contributions fit the free image at the flush");
 // diagnostic builds: lsm_block_params.reserved bit 0x20 makes every run take the group loop (the u8 has no
 // unused bit; this one is otherwise read only by the fused instantiation's look-back, which has no wave loop)
 constexpr uint32_t kDiagNoWaveBlocks = 0x20;
@@ -2198,8 +2208,9 @@ __global__ __launch_bounds__(kGThreads) __attribute__((amdgpu_waves_per_eu(4))) 
   // ---- The wave-per-block loop.  A run whose every block is group-class, has at most
   // kWItems items, fits a wave slot (wave_fits) and ends at or before out_cap is written
   // wave per block: wave w takes blocks w, w + 4, ... of the run, lane = item, the four DPP
-  // rows of the wave hash the payload's 1 KiB units, a lane quad runs the scramble chain
-  // and writes the header, and the wave copies its block out.  Any other run (listed, bad,
+  // rows of the wave hash the payload's 1 KiB units, and the wave copies the payload out;
+  // once per kWDefer of its blocks a lane quad per block runs the scramble chain and the
+  // rest of the checksum and writes the header to the output.  Any other run (listed, bad,
   // oversize or overflowing blocks, mixed batches) takes the group loop below, untouched.
   // The choice is a ballot over the run registers, which every wave holds alike, so it is
   // uniform over the workgroup.
@@ -2243,6 +2254,60 @@ __global__ __launch_bounds__(kGThreads) __attribute__((amdgpu_waves_per_eu(4))) 
         wave_items(r, raw);
       }
       vm_wait<0>();
+      // Deferred checksums and headers: what follows a block's row hashing (the scramble
+      // chain, the merge, the avalanche, the header checksum and the header bytes) is one
+      // instruction stream for a lane quad, so it runs once per kWDefer blocks of the wave, a
+      // quad per block, instead of once per block in all sixteen quads.  Until then the wave
+      // keeps, per block, the 40 contribution words of a long payload (lane x: word x, two
+      // VGPRs per kept block), or in quad j the finished digest of the j-th kept block's
+      // payload of <= 240 B (the short path reads the image, so it runs at block time).
+      uint64_t d0 = 0, d1 = 0;
+      uint64_t kc[kWDefer] = {};
+      uint32_t dn = 0, dr = wave;  // blocks kept since the last flush; the first one's place in the run
+      auto flush_headers = [&]() {  // (every lane active: quad_sum64 and the shuffles read other lanes)
+        const uint32_t rj = dr + kGWaves * ((uint32_t)lane >> 2);
+        const int q = lane & 3;
+        const bool in = ((uint32_t)lane >> 2) < dn;
+        const uint64_t ob = lane_u64(r_off, rj);
+        const uint32_t plen = (uint32_t)(lane_u64(r_off, rj + 1) - ob) - kHdrLen;
+        const bool lng = in && plen > 240;
+        uint64_t lo = 0, hi = 0;
+        // the kept contributions go to the image, which is free after the copy-out, and quad j
+        // runs block j's chain over them as the group loop's chain wave does (its batch's
+        // read-ahead past a block's units stays inside the kept words, unused)
+        constexpr uint32_t kCW = kWUnits * 8;
+        uint64_t* const side = reinterpret_cast<uint64_t*>(W.img);
+        if ((uint32_t)lane < kCW) {
+#pragma unroll
+          for (uint32_t s = 0; s < kWDefer; ++s) side[kCW * s + (uint32_t)lane] = kc[s];
+        }
+        wave_lds_wait();
+        if (lng) {
+          const uint32_t nbk = (plen - 1) / 1024;
+          uint64_t a0, a1;
+          xxh3_acc_init(q, a0, a1);
+          const uint64_t scr0 = L.secret.acc[16 + 2 * q], scr1 = L.secret.acc[16 + 2 * q + 1];
+          static_assert((kWImg - 1) / 1024 <= 4 && 4 <= kWUnits, "nbk <= 4: one batch is the whole chain");
+          const uint64_t* cb = side + kCW * ((uint32_t)lane >> 2) + 2 * q;
+          const uint64_t t0 = cb[8 * nbk], t1 = cb[8 * nbk + 1];
+          xxh3_quad_chain_batch<4>(cb, 0, nbk, scr0, scr1, a0, a1);
+          d0 = a0 + t0;
+          d1 = a1 + t1;
+        }
+        if (lng) xxh3_merge_part(&L.secret, q, d0, d1, lo, hi);
+        lo = quad_sum64(lo);
+        hi = quad_sum64(hi);
+        if (in) {
+          if (lng) {
+            xxh3_finish128(plen, lo, hi, lo, hi);
+          } else {
+            lo = d0;
+            hi = d1;
+          }
+          write_header_quad((__attribute__((address_space(1))) uint8_t*)(P.out + ob), 0, P.type, lo, hi, plen, q);
+          if (q == 0) P.status[b_begin + rj] = ST_OK;
+        }
+      };
       while (r < nr) {
         const uint32_t i0 = rl32(r_start, r), n = rl32(r_start, r + 1) - i0;
         const uint64_t kbase = rl64(r_ks, r) & ~15ULL, vbase = rl64(r_vs, r) & ~15ULL;
@@ -2280,8 +2345,6 @@ __global__ __launch_bounds__(kGThreads) __attribute__((amdgpu_waves_per_eu(4))) 
         // the stage is free: the next block's DMA runs under the hash, the chain and the copy-out
         if (more) wave_dma(rn);
         // ---- payload xxh3_128: the wave's four DPP rows take the 1 KiB units
-        uint64_t lo = 0, hi = 0;
-        const int q = lane & 3;
         if (plen > 240) {
           const uint32_t nbk = (plen - 1) / 1024;
           {
@@ -2290,56 +2353,47 @@ __global__ __launch_bounds__(kGThreads) __attribute__((amdgpu_waves_per_eu(4))) 
               uint64_t c0, c1;
               xxh3_row_unit(W.img, p0, plen, nbk, u, rr, &L.secret, c0, c1);
               if (rr < 4) {
-                W.contrib[8 * u + 2 * q] = c0;
-                W.contrib[8 * u + 2 * q + 1] = c1;
+                W.contrib[8 * u + 2 * rr] = c0;
+                W.contrib[8 * u + 2 * rr + 1] = c1;
               }
             }
           }
           wave_lds_wait();
-          // ---- the scramble chain and the merge: every quad computes the same (lane q holds
-          // accumulator pair q; the reads are LDS broadcasts), quad 0 writes the header
-          uint64_t a0, a1;
-          xxh3_acc_init(q, a0, a1);
-          const uint64_t scr0 = L.secret.acc[16 + 2 * q], scr1 = L.secret.acc[16 + 2 * q + 1];
-          // one batch is the whole chain, and its read-ahead past the block's units stays in W.contrib
-          static_assert((kWImg - 1) / 1024 <= 4 && 4 <= kWUnits, "nbk <= 4");
-          const uint64_t* cb = W.contrib + 2 * q;
-          const uint64_t t0 = cb[8 * nbk], t1 = cb[8 * nbk + 1];
-          xxh3_quad_chain_batch<4>(cb, 0, nbk, scr0, scr1, a0, a1);
-          a0 += t0;
-          a1 += t1;
-          xxh3_merge_part(&L.secret, q, a0, a1, lo, hi);
-        }
-        lo = quad_sum64(lo);  // (every lane: DPP reads of inactive lanes are undefined)
-        hi = quad_sum64(hi);
-        if (lane < 4) {
-          if (plen > 240) {
-            xxh3_finish128(plen, lo, hi, lo, hi);
-          } else {
-            xxh3_128_short(plen, BaseReader8{W.img, p0}, BaseReader64{W.img, p0}, lo, hi);
+          // the block's contributions, lane x word x, into the registers of kept block dn
+          {
+            const uint64_t cv = W.contrib[min((uint32_t)lane, kWUnits * 8 - 1)];
+#pragma unroll
+            for (uint32_t s = 0; s < kWDefer; ++s) kc[s] = dn == s ? cv : kc[s];
           }
-          write_header_quad(W.img, pad, P.type, lo, hi, plen, q);
-          if (lane == 0) P.status[b_begin + r] = ST_OK;
+        } else if (((uint32_t)lane >> 2) == dn) {  // (the short path reads the image, so it runs now)
+          xxh3_128_short(plen, BaseReader8{W.img, p0}, BaseReader64{W.img, p0}, d0, d1);
         }
-        wave_lds_wait();
+        ++dn;
         // the next block's DMA pieces and item fields, before this block's stores are
         // issued: the stores never count in this wait
         vm_wait<0>();
-        // ---- copy-out: the whole 16-B pieces [c0, c1), then the partial pieces at the
-        // block's two ends with one masked byte store each (lane x stores byte x; the
-        // rest of those pieces belongs to the neighbouring blocks)
+        // ---- copy-out of the payload [p0, end); the header's 33 bytes are stored by
+        // flush_headers alone, so no output byte is stored twice.  The whole 16-B pieces
+        // [ch, c1) past the header, then the partial pieces at the payload's two ends with
+        // one masked byte store each (lane x stores byte x of the piece; the rest of those
+        // pieces is header, or belongs to the next block)
         {
-          const uint32_t end = pad + total, c0 = (pad + 15) >> 4, c1 = end >> 4;
+          const uint32_t end = pad + total, ch = (p0 + 15) >> 4, c1 = end >> 4;
           const u32x4* const csrc = reinterpret_cast<const u32x4*>(W.img);
           u32x4* const cdst = reinterpret_cast<u32x4*>(dabs & ~15ULL);
-          for (uint32_t c = c0 + (uint32_t)lane; c < c1; c += kWave)
+          for (uint32_t c = ch + (uint32_t)lane; c < c1; c += kWave)
             *(__attribute__((address_space(1))) u32x4*)(cdst + c) = csrc[c];
           auto* gb = (__attribute__((address_space(1))) uint8_t*)cdst;
           const uint32_t x = (uint32_t)lane;
-          if (x >= pad && x < min(16 * c0, end)) gb[x] = W.img[x];
-          if (c1 >= c0 && 16 * c1 + x < end) gb[16 * c1 + x] = W.img[16 * c1 + x];
+          if (p0 + x < min(16 * ch, end)) gb[p0 + x] = W.img[p0 + x];
+          if (c1 >= ch && 16 * c1 + x < end) gb[16 * c1 + x] = W.img[16 * c1 + x];
         }
         wave_lds_wait();  // (the image is read out before the next block's records are written)
+        if (dn == kWDefer || !more) {
+          flush_headers();
+          dn = 0;
+          dr = rn;
+        }
         r = rn;
       }
       return;
