@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """Encode ablations on a diagnostic build (LSMGPU_LIB=...libdiag.so): kernel
-time with parts of the group kernel's record writer dropped (outputs invalid).
-Bits (lsm_block_params.reserved, u8): 1 all record stores, 0x20 value copies,
-0x40 key copies, 0x60 header varints, 2 hash/header, 4 copy-out."""
+time with phases of the group kernel's group loop dropped (outputs invalid).
+Bits (lsm_block_params.reserved, u8; the table is in csrc/encode_common.hpp):
+1 no record stores, 2 no hash / header, 4 no copy-out, 8 no records and no
+tails, 16 no next-group DMA, 0x20 the group loop only (no wave-per-block loop;
+in the fused instantiation: the look-back gives up), 0x40 / 0x80 phase timers.
+Any ablation bit keeps a run off the wave-per-block loop, so the ablations are
+compared with the 0x20 run, not with the full one."""
 import sys
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
@@ -11,6 +15,10 @@ for p in (ROOT, ROOT / "lsm-tree_amd", ROOT / "oracle", ROOT / "tests"):
 import torch  # noqa: E402
 import bench  # noqa: E402
 import lsmgpu  # noqa: E402
+
+# csrc/encode_common.hpp, mirrored
+DIAG_NO_RECORD_STORES, DIAG_NO_HASH, DIAG_NO_COPY_OUT, DIAG_NO_RECORDS_TAILS, DIAG_NO_NEXT_DMA = 1, 2, 4, 8, 16
+DIAG_NO_WAVE_BLOCKS = 0x20
 
 
 def main():
@@ -28,9 +36,10 @@ def main():
     enc_ctx = lsmgpu.Encoder()
     enc = enc_ctx.encode(items, starts, nb)
     torch.cuda.synchronize()
-    bits_list = [(0, "full"), (0x20, "no value copy"), (0x40, "no key copy"), (0x60, "no header varints"),
-                 (1, "no record stores"), (2, "no hash/header"), (4, "no copy-out"),
-                 (7, "none of records/hash/copy-out")]
+    bits_list = [(0, "full"), (DIAG_NO_WAVE_BLOCKS, "group loop only"), (DIAG_NO_RECORD_STORES, "no record stores"),
+                 (DIAG_NO_HASH, "no hash/header"), (DIAG_NO_COPY_OUT, "no copy-out"),
+                 (DIAG_NO_RECORD_STORES | DIAG_NO_HASH | DIAG_NO_COPY_OUT, "none of records/hash/copy-out"),
+                 (DIAG_NO_RECORDS_TAILS, "no records and no tails"), (DIAG_NO_NEXT_DMA, "no next-group DMA")]
     res = {b: [] for b, _ in bits_list}
     for r in range(3):
         for bits, name in bits_list:
@@ -45,9 +54,10 @@ def main():
             torch.cuda.synchronize()
             res[bits].append(e0.elapsed_time(e1) / 5)
     lsmgpu.LsmBlockParams = orig
+    base = sorted(res[DIAG_NO_WAVE_BLOCKS])[1]
     for bits, name in bits_list:
         v = sorted(res[bits])[1]
-        print(f"{which} {name:32s} {v:.4f} ms  (delta vs full {v - sorted(res[0])[1]:+.4f})")
+        print(f"{which} {name:32s} {v:.4f} ms  (delta vs the group loop {v - base:+.4f})")
 
 
 if __name__ == "__main__":

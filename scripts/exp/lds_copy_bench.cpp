@@ -13,7 +13,7 @@
 //                the lane has it, the head and tail bytes by 0
 //  10 uni-carry  the same loop, each source dword read once (carried; a select at the wrap)
 //  11 uni-r2-u8  9 unrolled by 8
-// (9-11 as encode.hip's lds_copy_uniform: the last step of a B that is no multiple of the
+// (9-11 as encode_group.hpp's lds_copy_uniform: the last step of a B that is no multiple of the
 // unroll wraps on over dwords already copied instead of a remainder loop)
 // Each variant's image is checked against a host reference.
 #include <hip/hip_runtime.h>

@@ -13,6 +13,10 @@ import torch  # noqa: E402
 import bench  # noqa: E402
 import lsmgpu  # noqa: E402
 
+# lsm_block_params.reserved in a diagnostic build: csrc/encode_common.hpp, mirrored
+DIAG_NO_RECORD_STORES, DIAG_NO_HASH, DIAG_NO_COPY_OUT, DIAG_NO_RECORDS_TAILS, DIAG_NO_NEXT_DMA = 1, 2, 4, 8, 16
+DIAG_GROUP_PHASES = 0x80
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -56,7 +60,7 @@ def main():
         import ctypes as C
         L = lsmgpu.lib()
         orig = lsmgpu.LsmBlockParams
-        lsmgpu.LsmBlockParams = lambda ri, bt, c, r, hr, *f: orig(ri, bt, c, 0x80, hr, *f)
+        lsmgpu.LsmBlockParams = lambda ri, bt, c, r, hr, *f: orig(ri, bt, c, DIAG_GROUP_PHASES, hr, *f)
         buf = (C.c_uint64 * 16)()
         rc0 = L.lsm_diag_encode_phases(buf)
         enc_ctx.encode(items, starts, nb, out=enc)
@@ -74,9 +78,13 @@ def main():
     if args.ablate:
         import ctypes as C
         L = lsmgpu.lib()
-        for bits, name in ((1, "no record stores"), (2, "no hash/header"), (4, "no copy-out"), (7, "none of them"),
-                           (8, "no group compute"), (12, "no compute/copy-out"), (16, "no next-group DMA"),
-                           (28, "barriers + item loads")):
+        for bits, name in ((DIAG_NO_RECORD_STORES, "no record stores"), (DIAG_NO_HASH, "no hash/header"),
+                           (DIAG_NO_COPY_OUT, "no copy-out"),
+                           (DIAG_NO_RECORD_STORES | DIAG_NO_HASH | DIAG_NO_COPY_OUT, "none of them"),
+                           (DIAG_NO_RECORDS_TAILS, "no records and no tails"),
+                           (DIAG_NO_RECORDS_TAILS | DIAG_NO_COPY_OUT, "no compute/copy-out"),
+                           (DIAG_NO_NEXT_DMA, "no next-group DMA"),
+                           (DIAG_NO_RECORDS_TAILS | DIAG_NO_COPY_OUT | DIAG_NO_NEXT_DMA, "barriers + item loads")):
             orig = lsmgpu.LsmBlockParams
             class P2(C.Structure):  # noqa: E306
                 _fields_ = orig._fields_

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-phase s_memtime totals of encode_huge_records_kernel, wave 0 of each
 workgroup (diagnostic build: LSMGPU_LIB=lsm-tree_amd/.variants/libdiag.so,
-lsm_block_params.reserved bit 0x40), on the bench's 1 MiB / 4 MiB batches."""
+lsm_block_params.reserved bit kDiagRecPhases), on the bench's 1 MiB / 4 MiB batches."""
 import ctypes as C
 import sys
 from pathlib import Path
@@ -15,6 +15,7 @@ import torch  # noqa: E402
 import bench  # noqa: E402
 import lsmgpu  # noqa: E402
 
+DIAG_REC_PHASES = 0x40  # kDiagRecPhases, csrc/encode_common.hpp
 NAMES = {6: "loop / edges", 0: "unit lookup", 1: "records -> LDS", 2: "barrier", 3: "contributions",
          4: "copy-out", 5: "tail unit"}
 torch.cuda.set_device(0)
@@ -27,7 +28,7 @@ for name, nb, ipb in (("1MiB", 240, 13108), ("4MiB", 60, 52429)):
     out = enc.encode(items, starts, nb)
     torch.cuda.synchronize()
     L.lsm_diag_encode_phases(buf)
-    lsmgpu.LsmBlockParams = lambda ri, bt, c, r, hr: orig(ri, bt, c, 0x40, hr)
+    lsmgpu.LsmBlockParams = lambda ri, bt, c, r, hr: orig(ri, bt, c, DIAG_REC_PHASES, hr)
     enc.encode(items, starts, nb, out=out)
     torch.cuda.synchronize()
     lsmgpu.LsmBlockParams = orig

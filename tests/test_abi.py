@@ -89,6 +89,23 @@ def test_workspace_sizes_monotone(L):
     assert lib.lsm_encode_workspace_size(10, 1) <= lib.lsm_encode_workspace_size(10 << 20, 1 << 18)
 
 
+def test_encode_workspace_sizes_unchanged(L):
+    """The encode workspace's regions are listed once (EncodeWorkspace, csrc/encode_common.hpp); both
+    size functions still return, over a grid of edge sizes, what the library returned when the sum
+    and the carve were written separately (tests/golden/encode_workspace_sizes.json)."""
+    import json
+    lib = L.lib()
+    gold = json.loads((ROOT / "tests" / "golden" / "encode_workspace_sizes.json").read_text())
+    rows = {(ni, nb): (size, ex) for ni, nb, size, ex in gold["rows"]}
+    assert gold["out_cap"] == [0, 32767, 32768, 1 << 30]
+    for ni in (0, 1, 63, 64, 65, 4097, 1 << 20):
+        for nb in (1, 2, 255, 256, 257, 1 << 18):
+            size, ex = rows[(ni, nb)]
+            assert lib.lsm_encode_workspace_size(ni, nb) == size, (ni, nb)
+            for oc, want in zip(gold["out_cap"], ex):
+                assert lib.lsm_encode_workspace_size_ex(ni, nb, oc) == want, (ni, nb, oc)
+
+
 def test_bad_args_rejected_without_device(L):
     """Argument validation happens before any HIP call."""
     import ctypes as C

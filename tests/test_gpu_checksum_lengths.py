@@ -33,7 +33,7 @@ from helpers import compare_decode, counter_items, gpu_decode
 
 HDR = 33
 RUN = 32                       # kGRun: blocks per workgroup of the group kernel
-W_IMG, G_IMG, BIG = 4496, 15872, 96 * 1024   # kWImg, kGImg, kImgBig (csrc/encode.hip)
+W_IMG, G_IMG, BIG = 4496, 15872, 96 * 1024   # kWImg (csrc/encode_group.hpp), kGImg, kImgBig (csrc/encode_common.hpp)
 ST_CKSUM = 4
 
 WAVE = (list(range(236, 261)) + list(range(1020, 1031)) + list(range(1084, 1095)) +

@@ -1,5 +1,5 @@
 """Deferred scramble chains, checksum tails and headers in the group kernel's wave-per-block
-loop (csrc/encode.hip, flush_headers): a wave stores a block's payload at block time and no
+loop (csrc/encode_group.hpp, flush_headers): a wave stores a block's payload at block time and no
 header byte; it keeps the block's 40 contribution words in registers (or, in lane quad j,
 the finished digest of a payload of <= 240 B), and after every kWDefer = 4 of its blocks,
 or its last one of the run, quad j runs the j-th kept block's chain, merge, avalanche and
@@ -26,7 +26,7 @@ PER = 52    # items per 4 KiB block of 16 B keys / 64 B values
 RUN = 32    # kGRun: blocks per workgroup
 WAVES = 4   # kGWaves: wave w takes blocks w, w + 4, ... of a run
 HDR = 33    # block header bytes
-# csrc/encode.hip, mirrored (wave_fits): n <= 64 items, span + 15 <= limit for the key span,
+# csrc/encode_group.hpp, mirrored (wave_fits): n <= 64 items, span + 15 <= limit for the key span,
 # the value span and the encoded size, each counted from the 16-B boundary at or before its start
 W_ITEMS, W_KEYS, W_VALS, W_IMG = 64, 1024, 4096, 4496
 DIAG_NO_WAVE_BLOCKS = 0x20

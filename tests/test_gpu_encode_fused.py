@@ -1,6 +1,6 @@
 """The run-level plan fused into the encode group kernel (encode_group_kernel<..., true>):
 each 32-block run plans its own blocks and takes its output offset from the runs before it
-by a decoupled look-back (csrc/encode.hip run_lookback), with no plan launch and no size
+by a decoupled look-back (csrc/encode_group.hpp run_lookback), with no plan launch and no size
 scan.  Taken for data blocks without a hash index, <= 512 items per block on average, no
 pool, when asked for (LSM_ENCODE_RUN_PLAN, as here) or at >= 128 items per block.  Every case is bit-exact against the oracle (DataBlock::encode_into +
 Block::write_into, src/table/data_block/mod.rs:523-549, src/table/block/mod.rs:45-84),
@@ -49,7 +49,7 @@ def _encode(gpu, items, starts, off32, ri=16, reserved=0, lib=None):
     assert rc == 0, rc
     torch.cuda.synchronize()
     o = off.cpu().numpy().view(np.uint64)
-    # the look-back words (the workspace's sizes array on this path, encode.hip launch_encode)
+    # the look-back words (the workspace's sizes array on this path, encode_plan.hip launch_encode_plan)
     runs = (nb + RUN - 1) // RUN
     base = 2 * _al256((nb + 1) * 8)
     lb = ws[base:base + 8 * runs].cpu().numpy().view(np.uint64)

@@ -1,4 +1,4 @@
-"""The group kernel's value copy (csrc/encode.hip lds_copy_uniform + lds_copy): the
+"""The group kernel's value copy (csrc/encode_group.hpp lds_copy_uniform + lds_copy): the
 interior dwords that every value-carrying lane of a wave has are copied in a loop with
 a wave-uniform trip count B (the wave-wide minimum), the head bytes, each lane's surplus
 dwords and the tail bytes by the general loop; under kUniformMin = 4 dwords, or with no

@@ -1,4 +1,4 @@
-"""The group kernel's wave-per-block loop (csrc/encode.hip, encode_group_kernel without a
+"""The group kernel's wave-per-block loop (csrc/encode_group.hpp, encode_group_kernel without a
 hash index or the fused plan): a 32-block run whose every block is group-class, has at most
 64 items, fits a wave slot (wave_fits: kWKeys / kWVals / kWImg) and ends at or before
 out_cap is written one wave per block, wave w taking blocks w, w + 4, ... of the run, with
@@ -23,7 +23,7 @@ pytestmark = pytest.mark.gpu
 
 PER = 52   # items per 4 KiB block of 16 B keys / 64 B values
 RUN = 32   # kGRun: blocks per workgroup
-# csrc/encode.hip, mirrored: a block takes the wave loop with n <= 64 items and
+# csrc/encode_group.hpp, mirrored: a block takes the wave loop with n <= 64 items and
 # span + 15 <= limit for its key span, value span and encoded size, each span counted
 # from the 16-B boundary at or before its start (wave_fits)
 W_ITEMS, W_KEYS, W_VALS, W_IMG = 64, 1024, 4096, 4496
