@@ -37,6 +37,10 @@
  *   lsm_scan_table     <- Scanner::new / next      src/table/scanner.rs:24-92 (block handles from the
  *                         block index: FullBlockIndex / TwoLevelBlockIndex, src/table/block_index/,
  *                         regions from the TOC, src/table/regions.rs:55-76)
+ *   lsm_merge_runs     <- Merger::new / next       src/merge.rs:34-100
+ *                         CompactionStream          src/compaction/stream.rs:46-221
+ *                         InternalKey Ord           src/key.rs:59-72
+ *                         (as composed in compaction/worker.rs:149-182,389-390)
  *   lsm_bloom_shape    <- BloomConstructionPolicy::init  src/table/filter/mod.rs:25-34
  *   lsm_hash64_keys    <- FullFilterWriter::register_key src/table/writer/filter/full.rs:47-50
  *   lsm_bloom_build    <- standard_bloom Builder set_with_hash + build  builder.rs:33-53,154-170
@@ -575,6 +579,46 @@ int lsm_scan_table_async(const uint8_t* d_file, uint64_t file_len, const lsm_tab
                          uint32_t data_blocks_hint, const lsm_parsed_items* d_out, uint64_t item_cap, uint32_t* d_item_start, int32_t* d_status,
                          uint32_t* d_n_blocks, int32_t* d_table_status, void* d_workspace, size_t workspace_bytes,
                          void* stream);
+
+/* ---- merge of sorted runs with compaction GC ----------------------------------
+ * CompactionStream::new(Merger::new(runs), gc_seqno_threshold)
+ *     .evict_tombstones(flags & 1).zero_seqnos(flags & 2) with NoFilter
+ * (merge.rs:34-100, compaction/stream.rs:46-221), the step between the
+ * compaction read side and the writer (compaction/worker.rs:149-182,389-390;
+ * the memtable flush uses the same pair, abstract_tree.rs:98-105).
+ * Input: d_in holds every run back to back (keys, key_off, vals, val_off, seqno,
+ * vtype and n_items are used; both arenas readable LSM_INPUT_PADDING bytes past
+ * their end); run r is the items [d_run_start[r], d_run_start[r+1]) (n_runs + 1
+ * device u64, d_run_start[0] = 0, d_run_start[n_runs] = n_items; empty runs
+ * allowed), each sorted in InternalKey order (key.rs:59-72: user key ascending
+ * as unsigned bytes, a key before any longer key it prefixes, then seqno
+ * descending; equal neighbours are accepted).  n_items <= 2^32 - 2,
+ * 1 <= n_runs <= LSM_MERGE_MAX_RUNS, no other flag bit: else LSM_BAD_ARG.
+ * Output: an lsm_items-shaped SoA for lsm_cut_blocks / lsm_encode_blocks: item j
+ * is d_out_keys[d_out_key_off[j] .. d_out_key_off[j+1]), d_out_vals likewise,
+ * d_out_seqno[j], d_out_vtype[j]; entries 0 .. n_out of both offset arrays are
+ * written; *d_n_out (device) = n_out; d_out_src[j] (may be NULL) = the input index
+ * of output item j (the indices that never appear are the dropped items, what
+ * DroppedKvCallback::on_dropped would learn of).  The caller sizes the outputs
+ * for the input (n_items entries, n_items + 1 offsets, the input arenas' bytes
+ * + LSM_INPUT_PADDING): the output never exceeds the input.  Outputs must not
+ * overlap inputs.  Items with equal (key, seqno) in different runs (the
+ * reference's heap leaves their order open) come out lower run first.
+ * d_status[r] (n_runs device i32): LSM_OK, or LSM_BAD_ARG for a run that is not
+ * sorted (or a malformed d_run_start); if any run is rejected *d_n_out = 0 and
+ * the other outputs are unspecified.  n_items = 0 gives *d_n_out = 0.
+ * No host synchronisation.  Workspace: lsm_merge_workspace_size(n_items, n_runs). */
+#define LSM_MERGE_MAX_RUNS 64
+#define LSM_MERGE_EVICT_TOMBSTONES 1u  /* CompactionStream::evict_tombstones(true) */
+#define LSM_MERGE_ZERO_SEQNOS 2u       /* CompactionStream::zero_seqnos(true) */
+size_t lsm_merge_workspace_size(uint64_t n_items, uint32_t n_runs);
+int lsm_merge_runs(const lsm_items* d_in, const uint64_t* d_run_start, uint32_t n_runs,
+                   uint64_t gc_seqno_threshold, uint32_t flags,
+                   uint8_t* d_out_keys, uint64_t* d_out_key_off,
+                   uint8_t* d_out_vals, uint64_t* d_out_val_off,
+                   uint64_t* d_out_seqno, uint8_t* d_out_vtype,
+                   uint32_t* d_out_src, uint64_t* d_n_out, int32_t* d_status,
+                   void* d_workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

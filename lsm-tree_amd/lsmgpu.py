@@ -224,6 +224,13 @@ def lib():
         L.lsm_materialize_keys.restype = C.c_int
         L.lsm_materialize_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                            C.POINTER(LsmParsed), C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "lsm_merge_runs"):  # (variant builds of earlier trees lack it: A/B scripts)
+            L.lsm_merge_workspace_size.restype = C.c_size_t
+            L.lsm_merge_workspace_size.argtypes = [C.c_uint64, C.c_uint32]
+            L.lsm_merge_runs.restype = C.c_int
+            L.lsm_merge_runs.argtypes = [C.POINTER(LsmItems), C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         _lib = L
     return _lib
 
@@ -243,7 +250,8 @@ EXPORTED_SYMBOLS = ["lsm_abi_version", "lsm_status_name", "lsm_last_error", "lsm
                     "lsm_xxh3_128_stream_state_size", "lsm_xxh3_128_stream_workspace_size",
                     "lsm_xxh3_128_stream_init", "lsm_xxh3_128_stream_update", "lsm_xxh3_128_stream_digest",
                     "lsm_xxh3_128_stream_init_batch", "lsm_xxh3_128_stream_batch_workspace_size",
-                    "lsm_xxh3_128_stream_update_batch", "lsm_xxh3_128_stream_digest_batch"]
+                    "lsm_xxh3_128_stream_update_batch", "lsm_xxh3_128_stream_digest_batch",
+                    "lsm_merge_workspace_size", "lsm_merge_runs"]
 
 
 def _check(rc, what):
@@ -836,6 +844,78 @@ def items_to_device(items_np, device="cuda", off32=False):
     d["handle_off"] = torch.from_numpy(items_np.handle_off.view(np.int64)).to(device)
     d["handle_size"] = torch.from_numpy(items_np.handle_size.view(np.int32)).to(device)
     return d
+
+
+MERGE_MAX_RUNS, MERGE_EVICT_TOMBSTONES, MERGE_ZERO_SEQNOS = 64, 1, 2
+
+
+def merge_runs(items, run_start, gc_seqno_threshold=0, evict_tombstones=False, zero_seqnos=False, stream=None):
+    """CompactionStream::new(Merger::new(runs), gc_seqno_threshold).evict_tombstones(..).zero_seqnos(..)
+    (merge.rs:34-100, compaction/stream.rs:46-221) on the device.  items: device dict as
+    items_to_device returns it, every run back to back; run_start: int64 cuda [n_runs + 1] (or a
+    host sequence).  Returns a device dict of the same keys (keys, key_off, vals, val_off, seqno,
+    vtype, sized for the input: the first n_out items / n_out + 1 offsets are defined) plus
+    src (int32: input index of each output item), n_out (int64 [1], on the device) and status
+    (int32 [n_runs]).  No host synchronisation."""
+    torch = _torch()
+    dev = items["keys"].device
+    if not hasattr(run_start, "data_ptr"):
+        run_start = torch.tensor(list(run_start), dtype=torch.int64, device=dev)
+    n_runs = run_start.numel() - 1
+    n = items["seqno"].numel()
+    it = LsmItems()
+    held = []
+    for f in ("keys", "key_off", "vals", "val_off", "seqno", "vtype"):
+        t = items[f]
+        if t.numel() == 0:  # (an empty tensor has no address; the library wants every array non-NULL)
+            t = torch.zeros(1, dtype=t.dtype, device=dev)
+            held.append(t)
+        setattr(it, f, t.data_ptr())
+    it.n_items = n
+    out = {"keys": torch.empty(items["keys"].numel() + LSM_INPUT_PADDING, dtype=torch.uint8, device=dev),
+           "vals": torch.empty(items["vals"].numel() + LSM_INPUT_PADDING, dtype=torch.uint8, device=dev),
+           "key_off": torch.empty(n + 1, dtype=torch.int64, device=dev),
+           "val_off": torch.empty(n + 1, dtype=torch.int64, device=dev),
+           "seqno": torch.empty(max(n, 1), dtype=torch.int64, device=dev),
+           "vtype": torch.empty(max(n, 1), dtype=torch.uint8, device=dev),
+           "src": torch.empty(max(n, 1), dtype=torch.int32, device=dev),
+           "n_out": torch.empty(1, dtype=torch.int64, device=dev),
+           "status": torch.empty(max(n_runs, 1), dtype=torch.int32, device=dev)}
+    ws = torch.empty(lib().lsm_merge_workspace_size(n, max(n_runs, 0)), dtype=torch.uint8, device=dev)
+    flags = (MERGE_EVICT_TOMBSTONES if evict_tombstones else 0) | (MERGE_ZERO_SEQNOS if zero_seqnos else 0)
+    _check(lib().lsm_merge_runs(C.byref(it), _ptr(run_start), max(n_runs, 0), gc_seqno_threshold & (2 ** 64 - 1),
+                                flags, _ptr(out["keys"]), _ptr(out["key_off"]), _ptr(out["vals"]),
+                                _ptr(out["val_off"]), _ptr(out["seqno"]), _ptr(out["vtype"]), _ptr(out["src"]),
+                                _ptr(out["n_out"]), _ptr(out["status"]), _ptr(ws), ws.numel(), _stream(stream)),
+           "lsm_merge_runs")
+    ws.record_stream(torch.cuda.current_stream(dev) if stream is None else stream)
+    return out
+
+
+def decoded_to_items(blocks, block_off, n_blocks, out, keys, key_off):
+    """Decoder output -> encoder input: `out` from decode_blocks / scan_table over `blocks`
+    (block_off int64 cuda [n_blocks + 1]) plus materialize_keys' (keys, key_off) -> the device
+    lsm_items dict Encoder.encode and merge_runs take.  Keys as materialized; values gathered
+    from block_off[b] + 33 + val_off, val_len into a packed, padded arena.  Torch ops only
+    (plumbing: the hot stages around it are the decode and the merge)."""
+    torch = _torch()
+    dev = blocks.device
+    n = key_off.numel() - 1
+    starts = out["item_start"][:n_blocks + 1].to(torch.int64) & 0xFFFFFFFF
+    counts = starts[1:] - starts[:-1]
+    base = torch.repeat_interleave(block_off[:n_blocks].to(torch.int64) + LSM_HEADER_LEN, counts, output_size=n)
+    vlen = out["val_len"][:n].to(torch.int64) & 0xFFFFFFFF
+    vsrc = base + (out["val_off"][:n].to(torch.int64) & 0xFFFFFFFF)
+    val_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(vlen, 0, out=val_off[1:])
+    total = int(val_off[-1].item()) if n else 0
+    vals = padded_bytes(total, dev)
+    if total:
+        item = torch.repeat_interleave(torch.arange(n, device=dev), vlen, output_size=total)
+        pos = torch.arange(total, device=dev) - val_off[item]
+        vals[:total] = blocks[vsrc[item] + pos]
+    return {"keys": keys, "key_off": key_off, "vals": vals, "val_off": val_off,
+            "seqno": out["seqno"][:n].contiguous(), "vtype": out["vtype"][:n].contiguous()}
 
 
 def shard_blocks(block_off, world):
