@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import merge_model as M
+from merge_gpu import check, deal, gpu_merge, random_items, sort_run
 
 pytestmark = pytest.mark.gpu
 
@@ -21,86 +22,6 @@ LONG_VALUE = 256  # kMergeLong (csrc/merge.hip): values from this length on are 
 
 def case_rows(rows):
     return [(bytes.fromhex(k), bytes.fromhex(v), int(s), int(t)) for k, v, s, t in rows]
-
-
-def to_device(L, runs, key_skew=0, val_skew=0):
-    """Runs -> (device lsm_items dict, run_start list).  skew: the arena tensor starts that
-    many bytes into its allocation and the first item another skew bytes into the arena."""
-    import torch
-    flat = [it for r in runs for it in r]
-    n = len(flat)
-
-    def arena(parts, skew):
-        data = b"\xa5" * (2 * skew) + b"".join(parts)
-        off = np.concatenate([[0], np.cumsum([len(p) for p in parts], dtype=np.int64)]).astype(np.int64) + skew
-        return L.to_device_bytes(data)[skew:], torch.from_numpy(off).cuda()
-
-    keys, key_off = arena([it[0] for it in flat], key_skew)
-    vals, val_off = arena([it[1] for it in flat], val_skew)
-    d = {"keys": keys, "key_off": key_off, "vals": vals, "val_off": val_off,
-         "seqno": torch.from_numpy(np.array([it[2] for it in flat], np.uint64).view(np.int64)).cuda(),
-         "vtype": torch.from_numpy(np.array([it[3] for it in flat], np.uint8)).cuda()}
-    if n == 0:
-        d["seqno"] = torch.zeros(0, dtype=torch.int64).cuda()
-        d["vtype"] = torch.zeros(0, dtype=torch.uint8).cuda()
-    run_start = np.concatenate([[0], np.cumsum([len(r) for r in runs])]).astype(np.int64)
-    return d, run_start.tolist()
-
-
-def gpu_merge(L, runs, thr=0, evict=False, zero=False, key_skew=0, val_skew=0):
-    """Runs the merge; returns (items, src, status) read back from the device."""
-    import torch
-    d, run_start = to_device(L, runs, key_skew, val_skew)
-    out = L.merge_runs(d, run_start, thr, evict, zero)
-    torch.cuda.synchronize()
-    n_out = int(out["n_out"].cpu()[0])
-    status = out["status"].cpu().numpy()[:len(runs)].tolist()
-    ko = out["key_off"].cpu().numpy()[:n_out + 1]
-    vo = out["val_off"].cpu().numpy()[:n_out + 1]
-    assert ko[0] == 0 and vo[0] == 0
-    keys = out["keys"].cpu().numpy()[:int(ko[-1])].tobytes()
-    vals = out["vals"].cpu().numpy()[:int(vo[-1])].tobytes()
-    seq = out["seqno"].cpu().numpy().view(np.uint64)[:n_out]
-    vt = out["vtype"].cpu().numpy()[:n_out]
-    src = out["src"].cpu().numpy().view(np.uint32)[:n_out].tolist()
-    items = [(keys[int(ko[j]):int(ko[j + 1])], vals[int(vo[j]):int(vo[j + 1])], int(seq[j]), int(vt[j]))
-             for j in range(n_out)]
-    return items, src, status
-
-
-def check(L, runs, thr=0, evict=False, zero=False, **kw):
-    assert all(M.run_is_sorted(r) for r in runs)
-    want, want_src, dropped = M.merge_runs(runs, thr, evict, zero)
-    got, src, status = gpu_merge(L, runs, thr, evict, zero, **kw)
-    assert status == [0] * len(runs)
-    assert len(got) == len(want)
-    assert src == want_src
-    assert got == want
-    return want, dropped
-
-
-def sort_run(items):
-    return sorted(items, key=lambda it: (it[0], -it[2]))
-
-
-def random_items(rng, n, n_keys, key_len=(1, 24), val_len=(0, 80), max_seq=1000, vtypes=(0, 0, 0, 1, 2, 4)):
-    keys = set()
-    while len(keys) < n_keys:
-        keys.add(bytes(rng.choice(b"abcdefg\x00\xff") for _ in range(rng.randint(*key_len))))
-    keys = sorted(keys)
-    out = []
-    for _ in range(n):
-        t = rng.choice(vtypes)
-        v = b"" if t in (1, 2) else bytes(rng.getrandbits(8) for _ in range(rng.randint(*val_len)))
-        out.append((rng.choice(keys), v, rng.randrange(max_seq), t))
-    return out
-
-
-def deal(rng, items, n_runs):
-    runs = [[] for _ in range(n_runs)]
-    for it in items:
-        runs[rng.randrange(n_runs)].append(it)
-    return [sort_run(r) for r in runs]
 
 
 # ------------------------------------------------------------------- golden
