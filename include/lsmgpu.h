@@ -21,6 +21,12 @@
  *                         DataBlock::iter/Decoder  src/table/data_block/mod.rs:476, block/decoder.rs:442-483
  *                         IndexBlock::iter         src/table/index_block/mod.rs:91-95
  *   lsm_cut_blocks     <- Writer::write chunking   src/table/writer/mod.rs:243-296
+ *   lsm_cut_blocks_device <- the same rule on device offsets  src/table/writer/mod.rs:284-290,374
+ *                         PartitionedIndexWriter::register_data_block's partition cut
+ *                                                   src/table/writer/index/partitioned.rs:166-179
+ *   lsm_index_entries  <- KeyedBlockHandle of each spilled block  src/table/writer/mod.rs:332-337
+ *                         FullIndexWriter           src/table/writer/index/full.rs:55-69
+ *                         PartitionedIndexWriter (partitions, TLI)  src/table/writer/index/partitioned.rs:54-201
  *   lsm_xxh3_128_batch <- hash128                  src/hash.rs:7-9 (checksum of arbitrary byte ranges)
  *   lsm_point_read_blocks <- DataBlock::point_read src/table/data_block/mod.rs:412-472
  *   lsm_seek_blocks    <- data_block::Iter::seek / seek_upper (+ _exclusive)  data_block/iter.rs:37-176
@@ -594,7 +600,7 @@ int lsm_scan_table_async(const uint8_t* d_file, uint64_t file_len, const lsm_tab
  * as unsigned bytes, a key before any longer key it prefixes, then seqno
  * descending; equal neighbours are accepted).  n_items <= 2^32 - 2,
  * 1 <= n_runs <= LSM_MERGE_MAX_RUNS, no other flag bit: else LSM_BAD_ARG.
- * Output: an lsm_items-shaped SoA for lsm_cut_blocks / lsm_encode_blocks: item j
+ * Output: an lsm_items-shaped SoA for lsm_cut_blocks_device / lsm_encode_blocks: item j
  * is d_out_keys[d_out_key_off[j] .. d_out_key_off[j+1]), d_out_vals likewise,
  * d_out_seqno[j], d_out_vtype[j]; entries 0 .. n_out of both offset arrays are
  * written; *d_n_out (device) = n_out; d_out_src[j] (may be NULL) = the input index
@@ -619,6 +625,49 @@ int lsm_merge_runs(const lsm_items* d_in, const uint64_t* d_run_start, uint32_t 
                    uint64_t* d_out_seqno, uint8_t* d_out_vtype,
                    uint32_t* d_out_src, uint64_t* d_n_out, int32_t* d_status,
                    void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ---- table write side: block cut and block index on the device -------------------
+ * lsm_cut_blocks_device: lsm_cut_blocks on DEVICE offset arrays, e.g. the merge's
+ * outputs.  Item i weighs key_len + val_len + extra_per_item; a block is cut after
+ * the item at which the running weight reaches block_size (writer/mod.rs:284-290),
+ * the last partial block is flushed (:374).  d_val_off may be NULL (weight = key
+ * length + extra_per_item: with extra_per_item = size_of::<KeyedBlockHandle>() and
+ * block_size = the partition size this is PartitionedIndexWriter::register_data_block's
+ * rule over the index entries, partitioned.rs:166-179).  d_n_items may be NULL (n_items
+ * items); else it is a device count <= n_items, such as lsm_merge_runs' d_n_out: n_items
+ * is then only the arrays' capacity and entries past *d_n_items + 1 are never read.
+ * Writes d_block_item_start (entries 0 .. *d_n_blocks, at most cap_blocks + 1; always
+ * strictly increasing and at most the item count), *d_n_blocks (device u64) and
+ * *d_status (device i32): LSM_OK; LSM_BAD_ARG for an offset array that decreases
+ * (*d_n_blocks = 0); LSM_OVERFLOW for more than cap_blocks blocks (*d_n_blocks is the
+ * real count, only cap_blocks + 1 starts are written).  No items: *d_n_blocks = 0,
+ * d_block_item_start[0] = 0.  n_items <= 2^32 - 2, cap_blocks >= 1 with items, else
+ * LSM_BAD_ARG.  No host synchronisation, no wait between workgroups; may be captured
+ * into a graph.  Workspace: lsm_cut_workspace_size(n_items) bytes (8 per item). */
+size_t lsm_cut_workspace_size(uint64_t n_items);
+int lsm_cut_blocks_device(const uint64_t* d_key_off, const uint64_t* d_val_off, uint64_t n_items,
+                          const uint64_t* d_n_items, uint32_t extra_per_item, uint32_t block_size,
+                          uint32_t* d_block_item_start, uint64_t cap_blocks, uint64_t* d_n_blocks,
+                          int32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream);
+/* lsm_index_entries: the KeyedBlockHandles of an encoded batch (Writer::spill_block,
+ * writer/mod.rs:332-337): entry b = the key and seqno of the last item of block b
+ * (item d_block_item_start[b+1] - 1), handle_off = base_offset + d_block_off[b],
+ * handle_size = d_block_off[b+1] - d_block_off[b], with d_block_item_start /
+ * d_block_off as lsm_encode_blocks took / wrote them.  Only keys (readable
+ * LSM_INPUT_PADDING bytes past the end), key_off, seqno and n_items of d_items are
+ * read, so the same call over its own output and the partitions' offsets, with
+ * base_offset = the index region's file offset, gives the TLI entries
+ * (cut_index_block, partitioned.rs:80-84,113-115).  The outputs (d_out_key_off:
+ * n_blocks + 1, the others n_blocks entries) are the index form of lsm_items and
+ * feed lsm_encode_blocks with LSM_BLOCK_INDEX.  *d_result (device i32): LSM_OK, or
+ * LSM_OVERFLOW when the keys exceed key_cap: then only d_out_key_off is written.
+ * No host synchronisation.  Workspace: lsm_index_entries_workspace_size(n_blocks). */
+size_t lsm_index_entries_workspace_size(uint32_t n_blocks);
+int lsm_index_entries(const lsm_items* d_items, const uint32_t* d_block_item_start,
+                      const uint64_t* d_block_off, uint32_t n_blocks, uint64_t base_offset,
+                      uint8_t* d_out_keys, uint64_t key_cap, uint64_t* d_out_key_off,
+                      uint64_t* d_out_seqno, uint64_t* d_out_handle_off, uint32_t* d_out_handle_size,
+                      int32_t* d_result, void* d_workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

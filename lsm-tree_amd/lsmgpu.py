@@ -231,6 +231,19 @@ def lib():
             L.lsm_merge_runs.argtypes = [C.POINTER(LsmItems), C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        if hasattr(L, "lsm_cut_blocks_device"):  # (variant builds of earlier trees lack it: A/B scripts)
+            L.lsm_cut_workspace_size.restype = C.c_size_t
+            L.lsm_cut_workspace_size.argtypes = [C.c_uint64]
+            L.lsm_cut_blocks_device.restype = C.c_int
+            L.lsm_cut_blocks_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
+                                                C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_size_t, C.c_void_p]
+            L.lsm_index_entries_workspace_size.restype = C.c_size_t
+            L.lsm_index_entries_workspace_size.argtypes = [C.c_uint32]
+            L.lsm_index_entries.restype = C.c_int
+            L.lsm_index_entries.argtypes = [C.POINTER(LsmItems), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64,
+                                            C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         _lib = L
     return _lib
 
@@ -251,7 +264,9 @@ EXPORTED_SYMBOLS = ["lsm_abi_version", "lsm_status_name", "lsm_last_error", "lsm
                     "lsm_xxh3_128_stream_init", "lsm_xxh3_128_stream_update", "lsm_xxh3_128_stream_digest",
                     "lsm_xxh3_128_stream_init_batch", "lsm_xxh3_128_stream_batch_workspace_size",
                     "lsm_xxh3_128_stream_update_batch", "lsm_xxh3_128_stream_digest_batch",
-                    "lsm_merge_workspace_size", "lsm_merge_runs"]
+                    "lsm_merge_workspace_size", "lsm_merge_runs",
+                    "lsm_cut_workspace_size", "lsm_cut_blocks_device",
+                    "lsm_index_entries_workspace_size", "lsm_index_entries"]
 
 
 def _check(rc, what):
@@ -826,6 +841,131 @@ def cut_blocks(key_off, val_off, block_size):
     starts = np.zeros(n + 2, np.uint32)
     nb = lib().lsm_cut_blocks(key_off.ctypes.data, val_off.ctypes.data, n, block_size, starts.ctypes.data, n + 1)
     return starts[:nb + 1].copy()
+
+
+# Items per tile of lsm_cut_blocks_device (kCutTile, csrc/table_write.hip): tests size their inputs from it.
+CUT_TILE_ITEMS = 16384
+
+
+def cut_blocks_device(items_or_offsets, block_size, n_items=None, extra=0, stream=None):
+    """lsm_cut_blocks_device: the writer's cut rule on device offsets.  items_or_offsets: a device
+    lsm_items dict (key_off, val_off), or a (key_off, val_off) pair of int64 cuda tensors [cap + 1]
+    (val_off None: the weight is the key length + extra, the index partitions' rule).
+    n_items: None (every item of the arrays), an int, or a device int64 [1] count such as
+    merge_runs' n_out (the arrays are then only the capacity).  Reads back one 16-byte record
+    (block count and status) and returns the device int32 starts [n_blocks + 1]."""
+    torch = _torch()
+    if isinstance(items_or_offsets, dict):
+        key_off, val_off = items_or_offsets["key_off"], items_or_offsets.get("val_off")
+    else:
+        key_off, val_off = items_or_offsets
+    dev = key_off.device
+    cap = key_off.numel() - 1
+    d_n = None
+    if hasattr(n_items, "data_ptr"):
+        d_n = n_items
+    elif n_items is not None:
+        cap = int(n_items)
+    starts = torch.empty(cap + 1, dtype=torch.int32, device=dev)
+    res = torch.empty(2, dtype=torch.int64, device=dev)  # [n_blocks, status]
+    ws = torch.empty(lib().lsm_cut_workspace_size(cap), dtype=torch.uint8, device=dev)
+    _check(lib().lsm_cut_blocks_device(_ptr(key_off), _ptr(val_off), cap, _ptr(d_n), extra, block_size,
+                                       _ptr(starts), max(cap, 1), _ptr(res[0:]), _ptr(res[1:]), _ptr(ws),
+                                       ws.numel(), _stream(stream)), "lsm_cut_blocks_device")
+    ws.record_stream(torch.cuda.current_stream(dev) if stream is None else stream)
+    if stream is not None:
+        stream.synchronize()
+    nb, status = res.cpu().tolist()
+    _check(status & 0xFFFFFFFF, "lsm_cut_blocks_device (device status)")
+    return starts[:nb + 1]
+
+
+def index_entries(items, starts, block_off, n_blocks, base_offset=0, key_cap=None, stream=None):
+    """lsm_index_entries: the KeyedBlockHandles of an encoded batch as a device index-form lsm_items
+    dict (keys, key_off, seqno, handle_off, handle_size) for Encoder.encode(block_type=BLOCK_INDEX),
+    plus result (device int32 [1]: LSM_OK, or LSM_OVERFLOW when the keys exceed key_cap).  items:
+    device dict (keys padded, key_off, seqno); starts / block_off as Encoder.encode took / returned
+    them.  key_cap defaults to the items' key arena, which always suffices.  No host synchronisation."""
+    torch = _torch()
+    dev = items["keys"].device
+    n = items["seqno"].numel()
+    if key_cap is None:
+        key_cap = items["keys"].numel()
+    it = LsmItems()
+    it.keys, it.key_off, it.seqno, it.n_items = items["keys"].data_ptr(), items["key_off"].data_ptr(), \
+        items["seqno"].data_ptr(), n
+    out = {"keys": torch.zeros(key_cap + LSM_INPUT_PADDING, dtype=torch.uint8, device=dev),
+           "key_off": torch.empty(n_blocks + 1, dtype=torch.int64, device=dev),
+           "seqno": torch.empty(n_blocks, dtype=torch.int64, device=dev),
+           "handle_off": torch.empty(n_blocks, dtype=torch.int64, device=dev),
+           "handle_size": torch.empty(n_blocks, dtype=torch.int32, device=dev),
+           "result": torch.empty(1, dtype=torch.int32, device=dev)}
+    ws = torch.empty(lib().lsm_index_entries_workspace_size(n_blocks), dtype=torch.uint8, device=dev)
+    _check(lib().lsm_index_entries(C.byref(it), _ptr(starts), _ptr(block_off), n_blocks, base_offset,
+                                   _ptr(out["keys"]), key_cap, _ptr(out["key_off"]), _ptr(out["seqno"]),
+                                   _ptr(out["handle_off"]), _ptr(out["handle_size"]), _ptr(out["result"]), _ptr(ws),
+                                   ws.numel(), _stream(stream)), "lsm_index_entries")
+    ws.record_stream(torch.cuda.current_stream(dev) if stream is None else stream)
+    return out
+
+
+def write_table(items, block_size=4096, restart_interval=16, hash_ratio=0.0, two_level=False, partition_size=4096,
+                handle_overhead=48, n_items=None):
+    """The data and block-index regions of a table file, built on the device: what
+    pyoracle.table_write builds on the host (Writer::write / spill_block, writer/mod.rs:243-343;
+    FullIndexWriter::finish, writer/index/full.rs:55-69; PartitionedIndexWriter,
+    writer/index/partitioned.rs:54-201).  items: device lsm_items dict (keys and vals padded);
+    n_items: None, an int, or a device count such as merge_runs' n_out (the arrays are then the
+    capacity; no offset array is downloaded).  handle_overhead stands for
+    size_of::<KeyedBlockHandle>() in the partition cut (buffered size per handle = end key length
+    + handle_overhead), which the reference does not pin; the scan does not depend on where
+    partitions are cut.  Only scalars are read back: the block counts, the item count and the
+    region ends.  The filter, meta, TOC and trailer regions are not written.
+    Returns dict(file: uint8 cuda tensor (a view of a padded buffer), tli_off, tli_size,
+    index_off, data_len, block_count, block_off (data blocks, int64 cuda), starts (int32 cuda))."""
+    torch = _torch()
+    dev = items["keys"].device
+    starts = cut_blocks_device(items, block_size, n_items=n_items)
+    nb = starts.numel() - 1
+    if nb == 0:
+        raise LsmError("write_table: no items")
+    n = int(starts[nb].item())
+    items = dict(items, key_off=items["key_off"][:n + 1], val_off=items["val_off"][:n + 1],
+                 seqno=items["seqno"][:n], vtype=items["vtype"][:n])
+    items.pop("handle_off", None)
+    items.pop("handle_size", None)
+
+    def encode(it, st, count, **kw):
+        enc = Encoder(dev).encode(it, st, count, **kw)
+        end = int(enc["block_off"][count].item())
+        if not bool((enc["status"][:count] == 0).all().item()):
+            raise LsmError("write_table: a block failed to encode")
+        return enc, end
+
+    def one_block(count):
+        return torch.tensor([0, count], dtype=torch.int32, device=dev)
+
+    data, data_len = encode(items, starts, nb, restart_interval=restart_interval, hash_ratio=hash_ratio)
+    handles = index_entries(items, starts, data["block_off"], nb)
+    pieces = [data["buf"][:data_len]]
+    index_off = data_len
+    if two_level:
+        pstarts = cut_blocks_device((handles["key_off"], None), partition_size, extra=handle_overhead)
+        n_parts = pstarts.numel() - 1
+        parts, region_len = encode(handles, pstarts, n_parts, block_type=BLOCK_INDEX)
+        pieces.append(parts["buf"][:region_len])
+        handles = index_entries(handles, pstarts, parts["block_off"], n_parts, base_offset=index_off)
+        tli, tli_size = encode(handles, one_block(n_parts), 1, block_type=BLOCK_INDEX)
+        tli_off = index_off + region_len
+    else:
+        tli, tli_size = encode(handles, one_block(nb), 1, block_type=BLOCK_INDEX)
+        tli_off = index_off
+    pieces.append(tli["buf"][:tli_size])
+    total = tli_off + tli_size
+    file = padded_bytes(total, dev)
+    torch.cat(pieces, out=file[:total])
+    return {"file": file[:total], "tli_off": tli_off, "tli_size": tli_size, "index_off": index_off,
+            "data_len": data_len, "block_count": nb, "block_off": data["block_off"][:nb + 1], "starts": starts}
 
 
 def items_to_device(items_np, device="cuda", off32=False):
