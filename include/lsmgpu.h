@@ -40,6 +40,9 @@
  *   lsm_lz4_plan_framed / lsm_lz4_decompress_framed + lsm_decode_blocks_tuned(LSM_DECODE_PAYLOAD_VERIFIED)
  *                      <- Block::from_reader(Lz4) then DataBlock::new + iter   block/mod.rs:104-118, data_block/mod.rs:335,476
  *   lsm_materialize_plan / lsm_materialize_keys <- DataBlockParsedItem::materialize  data_block/mod.rs:296-315
+ *   lsm_materialize_items_plan / lsm_materialize_items
+ *                      <- the same producing the owned InternalValue (key and value) that Scanner::next
+ *                         yields (scanner.rs:74-92) into Merger::new (compaction/worker.rs:149-182)
  *   lsm_scan_table     <- Scanner::new / next      src/table/scanner.rs:24-92 (block handles from the
  *                         block index: FullBlockIndex / TwoLevelBlockIndex, src/table/block_index/,
  *                         regions from the TOC, src/table/regions.rs:55-76)
@@ -533,6 +536,64 @@ int lsm_materialize_keys_capped(const uint8_t* d_blocks, const uint64_t* d_block
                                 const uint32_t* d_item_start, const int32_t* d_status,
                                 const lsm_parsed_items* d_parsed, uint64_t n_items, const uint64_t* d_key_out_off,
                                 uint8_t* d_key_out, uint64_t key_cap, int32_t* d_result, void* stream);
+
+/* ---- materialize items: decoded blocks -> merge-ready item runs -------------------
+ * DataBlockParsedItem::materialize producing the owned InternalValue, key and
+ * value (data_block/mod.rs:296-315), as Scanner::next yields it (scanner.rs:74-92)
+ * into Merger::new (compaction/worker.rs:149-182): the parsed rows of one table are
+ * appended to an lsm_items-shaped SoA (what lsm_merge_runs and lsm_encode_blocks
+ * take) at a cursor held on the device.
+ * Inputs: the outputs of lsm_decode_blocks / lsm_scan_table(_async) over the same
+ * d_blocks (frames of lsm_lz4_decompress_framed decoded with
+ * LSM_DECODE_PAYLOAD_VERIFIED included); of d_parsed, key_off, key_len, prefix_len,
+ * val_off, val_len, seqno and vtype are required (else LSM_BAD_ARG).  n_items is the
+ * capacity of the parsed arrays.  The block count is n_blocks, or, when d_n_blocks
+ * is not NULL, the device count *d_n_blocks <= n_blocks that lsm_scan_table_async
+ * leaves; entries of d_item_start / d_status past the count are never read.  The
+ * row count R = min(d_item_start[count], n_items) is never read back.
+ * Cursor: d_base (device u64[3], NULL = {0, 0, 0}) = the {items, key bytes, value
+ * bytes} already in the outputs; d_end (device u64[3], not d_base itself) = d_base
+ * plus this table's {R, key bytes, value bytes}.  Passing table t's d_end as table
+ * t + 1's d_base appends the tables back to back; column 0 of a cursor array
+ * u64[n_tables + 1][3] is the d_run_start of lsm_merge_runs.
+ * Output row d_base[0] + i is parsed row i: key = prefix || suffix exactly as
+ * lsm_materialize_keys writes it, at d_out_key_off[d_base[0] + i] = d_base[1] + the
+ * key bytes of the rows before i (the entry at d_base[0] + R is d_end[1]); value =
+ * payload[val_off .. val_off + val_len) at d_out_val_off likewise; seqno and vtype
+ * copied.  The rows of a rejected block (d_status not LSM_OK, or a header type other
+ * than Data / Meta: an index block's val_len is a handle size, not a value) get an
+ * empty key, an empty value, seqno 0 and vtype 0, and so does a row whose key or
+ * value range does not lie inside its block's payload (a decode never produces one;
+ * a mismatched d_parsed cannot make the gather read outside d_blocks).
+ * lsm_materialize_items_plan writes the offsets and d_end; *d_result (device i32) =
+ * LSM_OK, or LSM_OVERFLOW when d_end[0] > out_item_cap (the offset arrays hold
+ * out_item_cap + 1 entries): then no offset is written and d_end still holds the
+ * real totals.  Workspace: lsm_materialize_items_workspace_size(n_items) bytes.
+ * lsm_materialize_items copies keys, values, seqnos and vtypes, all rows or none:
+ * *d_result = LSM_OVERFLOW and nothing is written when d_end[0] > out_item_cap,
+ * d_end[1] > key_cap or d_end[2] > val_cap.  No store touches a byte of either arena
+ * outside [d_base[k], d_end[k]) or a seqno / vtype entry outside
+ * [d_base[0], d_end[0]).  Arenas that feed lsm_merge_runs need LSM_INPUT_PADDING
+ * readable bytes past key_cap / val_cap.  One wave copies 64 consecutive rows,
+ * whatever blocks they lie in; a value of 256 bytes or more is copied by its whole
+ * wave (a single value is not split over waves).
+ * n_items = 0 or a count of 0: d_end = d_base, LSM_OK.  Both calls are asynchronous,
+ * do no host synchronisation, have no wait between workgroups and may be captured
+ * into a graph on one stream. */
+size_t lsm_materialize_items_workspace_size(uint64_t n_items);
+int lsm_materialize_items_plan(const uint8_t* d_blocks, const uint64_t* d_block_off, uint32_t n_blocks,
+                               const uint32_t* d_n_blocks, const uint32_t* d_item_start, const int32_t* d_status,
+                               const lsm_parsed_items* d_parsed, uint64_t n_items, const uint64_t* d_base,
+                               uint64_t* d_out_key_off, uint64_t* d_out_val_off, uint64_t out_item_cap,
+                               uint64_t* d_end, int32_t* d_result, void* d_workspace, size_t workspace_bytes,
+                               void* stream);
+int lsm_materialize_items(const uint8_t* d_blocks, const uint64_t* d_block_off, uint32_t n_blocks,
+                          const uint32_t* d_n_blocks, const uint32_t* d_item_start, const int32_t* d_status,
+                          const lsm_parsed_items* d_parsed, uint64_t n_items, const uint64_t* d_base,
+                          const uint64_t* d_end, const uint64_t* d_out_key_off, const uint64_t* d_out_val_off,
+                          uint8_t* d_out_keys, uint64_t key_cap, uint8_t* d_out_vals, uint64_t val_cap,
+                          uint64_t* d_out_seqno, uint8_t* d_out_vtype, uint64_t out_item_cap, int32_t* d_result,
+                          void* stream);
 
 /* ---- whole-table scan (Scanner, src/table/scanner.rs:24-92) -----------------
  * Decodes every data block of one table file image d_file[0 .. file_len) (16-byte

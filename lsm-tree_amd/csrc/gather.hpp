@@ -1,7 +1,8 @@
-// gather.hpp — byte gathers shared by the merge and the index-entry kernels:
-// a wave assembles the contiguous output span of its 64 items in LDS and stores
-// it 16 B per lane at any alignment (gather_field); long items are copied by
-// the whole wave (wave_copy).  Sources are read through 16-B aligned windows,
+// gather.hpp — byte gathers shared by the merge, the index-entry and the
+// materialize-items kernels: a wave assembles the contiguous output span of its
+// 64 items in LDS and stores it 16 B per lane at any alignment (gather_field =
+// lds_put + span_store, or gather_direct); long items are copied by the whole
+// wave (wave_copy).  Sources are read through 16-B aligned windows,
 // so a source arena must be readable LSM_INPUT_PADDING bytes past its end.
 #pragma once
 
@@ -55,30 +56,9 @@ __device__ __forceinline__ void wave_copy(const uint8_t* src, uint8_t* dst, uint
   if (done + lane < len) dst[done + lane] = src[done + lane];
 }
 
-// One field (keys or values) of one step: lane's item is src[0 .. len) ->
-// out[o .. o + len) (len 0 for dropped and idle lanes); the step's outputs are
-// the contiguous span out[o0 .. o1).
-__device__ __forceinline__ void gather_field(const uint8_t* src, uint32_t len, uint8_t* out, uint64_t o, uint64_t o0,
-                                             uint64_t o1, uint8_t* bf, uint32_t lane) {
-  if (o1 == o0) return;
-  const uint32_t pad = (uint32_t)(((uint64_t)(uintptr_t)out + o0) & 15);
-  uint64_t longs = __ballot(len >= kGatherLong);
-  if (longs || o1 - o0 + pad > kGatherBuf) {
-    // straight to global: long items by the whole wave, the others byte-wise by their lane
-    while (longs) {
-      const uint32_t l = (uint32_t)__builtin_ctzll(longs);
-      longs &= longs - 1;
-      const uint64_t sa = wave_readlane_u64((uint64_t)(uintptr_t)src, l);
-      const uint64_t da = wave_readlane_u64((uint64_t)(uintptr_t)(out + o), l);
-      const uint32_t ll = wave_readlane_u32(len, l);
-      wave_copy(reinterpret_cast<const uint8_t*>((uintptr_t)sa), reinterpret_cast<uint8_t*>((uintptr_t)da), ll, lane);
-    }
-    if (len < kGatherLong)
-      for (uint32_t t = 0; t < len; ++t) out[o + t] = src[t];
-    return;
-  }
-  // assemble the span in LDS at its global alignment, 16 source bytes at a time
-  const uint32_t rel = (uint32_t)(o - o0) + pad;
+// Lane-private part of a gather step: src[0 .. len) -> LDS d[0 .. len), 16 source
+// bytes at a time through aligned global windows (reads up to 31 bytes past src + len).
+__device__ __forceinline__ void lds_put(const uint8_t* src, uint32_t len, uint8_t* d) {
   if (len) {
     const uint64_t sa = (uint64_t)(uintptr_t)src;
     const uint32_t m = (uint32_t)(sa & 15);
@@ -89,13 +69,20 @@ __device__ __forceinline__ void gather_field(const uint8_t* src, uint32_t len, u
       uint64_t lo, hi;
       shift128(pack64(cur.x, cur.y), pack64(cur.z, cur.w), pack64(nxt.x, nxt.y), pack64(nxt.z, nxt.w), m, lo, hi);
       const uint32_t cnt = min(16u, len - 16 * c);
-      uint8_t* d = bf + rel + 16 * c;
+      uint8_t* dd = d + 16 * c;
 #pragma unroll
       for (uint32_t t = 0; t < 16; ++t)
-        if (t < cnt) d[t] = (uint8_t)((t < 8 ? lo : hi) >> (8 * (t & 7)));
+        if (t < cnt) dd[t] = (uint8_t)((t < 8 ? lo : hi) >> (8 * (t & 7)));
       cur = nxt;
     }
   }
+}
+
+// Wave part of a gather step: the span out[o0 .. o1), assembled by the lanes in
+// bf at its global alignment (bf[pad ..), pad = (out + o0) & 15), goes out 16 B
+// per lane, the partial pieces at both ends byte-wise.  Wave barriers on both sides.
+__device__ __forceinline__ void span_store(uint8_t* out, uint64_t o0, uint64_t o1, uint32_t pad, const uint8_t* bf,
+                                           uint32_t lane) {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
@@ -112,6 +99,37 @@ __device__ __forceinline__ void gather_field(const uint8_t* src, uint32_t len, u
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+}
+
+// Straight to global, for a step that holds a long item or overflows the LDS
+// buffer: long items by the whole wave, the others byte-wise by their lane.
+__device__ __forceinline__ void gather_direct(const uint8_t* src, uint32_t len, uint8_t* dst, uint32_t lane) {
+  uint64_t longs = __ballot(len >= kGatherLong);
+  while (longs) {
+    const uint32_t l = (uint32_t)__builtin_ctzll(longs);
+    longs &= longs - 1;
+    const uint64_t sa = wave_readlane_u64((uint64_t)(uintptr_t)src, l);
+    const uint64_t da = wave_readlane_u64((uint64_t)(uintptr_t)dst, l);
+    const uint32_t ll = wave_readlane_u32(len, l);
+    wave_copy(reinterpret_cast<const uint8_t*>((uintptr_t)sa), reinterpret_cast<uint8_t*>((uintptr_t)da), ll, lane);
+  }
+  if (len < kGatherLong)
+    for (uint32_t t = 0; t < len; ++t) dst[t] = src[t];
+}
+
+// One field (keys or values) of one step: lane's item is src[0 .. len) ->
+// out[o .. o + len) (len 0 for dropped and idle lanes); the step's outputs are
+// the contiguous span out[o0 .. o1).
+__device__ __forceinline__ void gather_field(const uint8_t* src, uint32_t len, uint8_t* out, uint64_t o, uint64_t o0,
+                                             uint64_t o1, uint8_t* bf, uint32_t lane) {
+  if (o1 == o0) return;
+  const uint32_t pad = (uint32_t)(((uint64_t)(uintptr_t)out + o0) & 15);
+  if (__ballot(len >= kGatherLong) || o1 - o0 + pad > kGatherBuf) {
+    gather_direct(src, len, out + o, lane);
+    return;
+  }
+  lds_put(src, len, bf + (uint32_t)(o - o0) + pad);
+  span_store(out, o0, o1, pad, bf, lane);
 }
 
 }  // namespace lsmgpu

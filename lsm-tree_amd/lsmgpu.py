@@ -224,6 +224,18 @@ def lib():
         L.lsm_materialize_keys.restype = C.c_int
         L.lsm_materialize_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                            C.POINTER(LsmParsed), C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "lsm_materialize_items"):  # (variant builds of earlier trees lack it: A/B scripts)
+            L.lsm_materialize_items_workspace_size.restype = C.c_size_t
+            L.lsm_materialize_items_workspace_size.argtypes = [C.c_uint64]
+            mi_inputs = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                         C.POINTER(LsmParsed), C.c_uint64, C.c_void_p]  # d_blocks .. d_base
+            L.lsm_materialize_items_plan.restype = C.c_int
+            L.lsm_materialize_items_plan.argtypes = mi_inputs + [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+            L.lsm_materialize_items.restype = C.c_int
+            L.lsm_materialize_items.argtypes = mi_inputs + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                            C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                            C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         if hasattr(L, "lsm_merge_runs"):  # (variant builds of earlier trees lack it: A/B scripts)
             L.lsm_merge_workspace_size.restype = C.c_size_t
             L.lsm_merge_workspace_size.argtypes = [C.c_uint64, C.c_uint32]
@@ -260,6 +272,7 @@ EXPORTED_SYMBOLS = ["lsm_abi_version", "lsm_status_name", "lsm_last_error", "lsm
                     "lsm_lz4_decompress_framed", "lsm_scan_workspace_size", "lsm_scan_table", "lsm_scan_table_async",
                     "lsm_materialize_workspace_size", "lsm_materialize_plan", "lsm_materialize_keys",
                     "lsm_materialize_keys_capped", "lsm_lz4_plan_capped",
+                    "lsm_materialize_items_workspace_size", "lsm_materialize_items_plan", "lsm_materialize_items",
                     "lsm_xxh3_128_stream_state_size", "lsm_xxh3_128_stream_workspace_size",
                     "lsm_xxh3_128_stream_init", "lsm_xxh3_128_stream_update", "lsm_xxh3_128_stream_digest",
                     "lsm_xxh3_128_stream_init_batch", "lsm_xxh3_128_stream_batch_workspace_size",
@@ -1032,12 +1045,132 @@ def merge_runs(items, run_start, gc_seqno_threshold=0, evict_tombstones=False, z
     return out
 
 
+def _mi_args(blocks, block_off, n_blocks, out):
+    """The leading arguments lsm_materialize_items_plan and lsm_materialize_items share (and the
+    struct they point into, which the caller keeps alive)."""
+    ps = LsmParsed()
+    for f, _ in PARSED_FIELDS:
+        setattr(ps, f, out[f].data_ptr() if f in out else None)
+    d_nb = n_blocks if hasattr(n_blocks, "data_ptr") else None
+    nb = out["item_start"].numel() - 1 if d_nb is not None else int(n_blocks)
+    return (_ptr(blocks), _ptr(block_off), nb, _ptr(d_nb), _ptr(out["item_start"]), _ptr(out["status"]),
+            C.byref(ps), out["key_off"].numel()), ps
+
+
+def _mi_plan(args, base, dst, item_cap, end, result, stream):
+    torch = _torch()
+    ws = torch.empty(lib().lsm_materialize_items_workspace_size(args[7]), dtype=torch.uint8, device=end.device)
+    _check(lib().lsm_materialize_items_plan(*args, _ptr(base), _ptr(dst["key_off"]), _ptr(dst["val_off"]), item_cap,
+                                            _ptr(end), _ptr(result), _ptr(ws), ws.numel(), _stream(stream)),
+           "lsm_materialize_items_plan")
+    ws.record_stream(torch.cuda.current_stream(end.device) if stream is None else stream)
+
+
+def _mi_gather(args, base, end, dst, caps, result, stream):
+    _check(lib().lsm_materialize_items(*args, _ptr(base), _ptr(end), _ptr(dst["key_off"]), _ptr(dst["val_off"]),
+                                       _ptr(dst["keys"]), caps[1], _ptr(dst["vals"]), caps[2], _ptr(dst["seqno"]),
+                                       _ptr(dst["vtype"]), caps[0], _ptr(result), _stream(stream)),
+           "lsm_materialize_items")
+
+
+def _mi_alloc(dev, item_cap, key_cap=None, val_cap=None):
+    torch = _torch()
+    d = {"key_off": torch.zeros(item_cap + 1, dtype=torch.int64, device=dev),
+         "val_off": torch.zeros(item_cap + 1, dtype=torch.int64, device=dev),
+         "seqno": torch.zeros(max(item_cap, 1), dtype=torch.int64, device=dev),
+         "vtype": torch.zeros(max(item_cap, 1), dtype=torch.uint8, device=dev)}
+    if key_cap is not None:
+        d["keys"], d["vals"] = padded_bytes(key_cap, dev), padded_bytes(val_cap, dev)
+    return d
+
+
+def materialize_items(blocks, block_off, n_blocks, out, base=None, into=None, caps=None, stream=None, end=None):
+    """lsm_materialize_items_plan + lsm_materialize_items: decode output `out` (dict from
+    decode_blocks / decode_lz4_blocks / scan_table over `blocks`) -> the device lsm_items dict
+    (keys, key_off, vals, val_off, seqno, vtype) that merge_runs and Encoder.encode take, plus
+    end (device int64 [3]: base + this table's {rows, key bytes, value bytes}), result and
+    plan_result (device int32 [1]: LSM_OK / LSM_OVERFLOW of the gather and of the plan).
+    n_blocks: an int, or the device count scan_table(sync=False) leaves.  base: device int64 [3]
+    cursor the rows are appended at (None = zeros); end: where to write the advanced cursor, e.g.
+    the next row of a cursor array (None = a fresh tensor).
+    Neither into nor caps: the arenas are sized from the plan (one read-back of `end`) and the
+    returned tensors are trimmed to the rows.  caps = (items, key bytes, value bytes): outputs
+    of that capacity, no host synchronisation, nothing trimmed.  into: an items dict (as this
+    call returned it) to append to in place; its capacities are its tensors' (the arenas' less
+    LSM_INPUT_PADDING) unless caps narrows them."""
+    torch = _torch()
+    dev = blocks.device
+    args, ps = _mi_args(blocks, block_off, n_blocks, out)
+    if end is None:
+        end = torch.zeros(3, dtype=torch.int64, device=dev)
+    result = torch.zeros(1, dtype=torch.int32, device=dev)
+    plan_result = torch.zeros(1, dtype=torch.int32, device=dev)
+    trim = None
+    if into is not None:
+        dst = into
+        if caps is None:
+            caps = (into["seqno"].numel(), into["keys"].numel() - LSM_INPUT_PADDING,
+                    into["vals"].numel() - LSM_INPUT_PADDING)
+        _mi_plan(args, base, dst, caps[0], end, plan_result, stream)
+    elif caps is not None:
+        dst = _mi_alloc(dev, *caps)
+        _mi_plan(args, base, dst, caps[0], end, plan_result, stream)
+    else:
+        if base is not None:
+            raise LsmError("materialize_items: a base needs `into` or `caps` (the outputs it already fills)")
+        dst = _mi_alloc(dev, args[7])
+        _mi_plan(args, None, dst, args[7], end, plan_result, stream)
+        if stream is not None:
+            stream.synchronize()
+        trim, key_cap, val_cap = end.cpu().tolist()
+        dst["keys"], dst["vals"] = padded_bytes(key_cap, dev), padded_bytes(val_cap, dev)
+        caps = (args[7], key_cap, val_cap)
+    _mi_gather(args, base, end, dst, caps, result, stream)
+    items = {f: dst[f] for f in ("keys", "key_off", "vals", "val_off", "seqno", "vtype")}
+    if trim is not None:
+        items.update(key_off=dst["key_off"][:trim + 1], val_off=dst["val_off"][:trim + 1],
+                     seqno=dst["seqno"][:trim], vtype=dst["vtype"][:trim])
+    items.update(end=end, result=result, plan_result=plan_result)
+    return items
+
+
+def tables_to_runs(tables, stream=None):
+    """Several decoded tables -> one merge-ready lsm_items dict, run after run: tables is a list
+    of (blocks, block_off, n_blocks, out) as materialize_items takes them.  The cursor
+    (int64 [n_tables + 1][3]) is chained on the device: table t + 1 is appended where table t
+    ended; only its last row (three scalars) is read back, to size the arenas and trim the
+    views.  Returns (items, run_start): items also holds result (device int32 [n_tables], the
+    gathers' LSM_OK / LSM_OVERFLOW); run_start is the device int64 [n_tables + 1] merge_runs takes."""
+    torch = _torch()
+    dev = tables[0][0].device
+    nt = len(tables)
+    cursor = torch.zeros((nt + 1, 3), dtype=torch.int64, device=dev)
+    calls = [_mi_args(*t) for t in tables]
+    item_cap = sum(a[7] for a, _ in calls)
+    dst = _mi_alloc(dev, item_cap)
+    plan_result = torch.zeros(nt, dtype=torch.int32, device=dev)
+    result = torch.zeros(nt, dtype=torch.int32, device=dev)
+    for t, (a, _) in enumerate(calls):
+        _mi_plan(a, cursor[t], dst, item_cap, cursor[t + 1], plan_result[t:], stream)
+    if stream is not None:
+        stream.synchronize()
+    n, key_cap, val_cap = cursor[nt].cpu().tolist()
+    dst["keys"], dst["vals"] = padded_bytes(key_cap, dev), padded_bytes(val_cap, dev)
+    for t, (a, _) in enumerate(calls):
+        _mi_gather(a, cursor[t], cursor[t + 1], dst, (item_cap, key_cap, val_cap), result[t:], stream)
+    items = {"keys": dst["keys"], "key_off": dst["key_off"][:n + 1], "vals": dst["vals"],
+             "val_off": dst["val_off"][:n + 1], "seqno": dst["seqno"][:n], "vtype": dst["vtype"][:n],
+             "result": result, "plan_result": plan_result}
+    return items, cursor[:, 0].contiguous()
+
+
 def decoded_to_items(blocks, block_off, n_blocks, out, keys, key_off):
     """Decoder output -> encoder input: `out` from decode_blocks / scan_table over `blocks`
     (block_off int64 cuda [n_blocks + 1]) plus materialize_keys' (keys, key_off) -> the device
     lsm_items dict Encoder.encode and merge_runs take.  Keys as materialized; values gathered
     from block_off[b] + 33 + val_off, val_len into a packed, padded arena.  Torch ops only
-    (plumbing: the hot stages around it are the decode and the merge)."""
+    (an index tensor per value byte and a host read-back: kept as an independent check of
+    materialize_items / tables_to_runs, the HIP path a pipeline uses)."""
     torch = _torch()
     dev = blocks.device
     n = key_off.numel() - 1
