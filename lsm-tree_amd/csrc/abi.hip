@@ -7,6 +7,7 @@
 
 #include "decode.hpp"
 #include "encode.hpp"
+#include "host_common.hpp"
 #include "lsmgpu.h"
 
 namespace {

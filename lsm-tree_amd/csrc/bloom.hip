@@ -18,8 +18,8 @@
 // the probe latency bound; neither is an HBM-streaming kernel.
 #include <hip/hip_runtime.h>
 
-#include "decode.hpp"
 #include "device_common.hpp"
+#include "host_common.hpp"
 #include "lsmgpu.h"
 
 namespace lsmgpu {

@@ -7,8 +7,9 @@
 
 #include <stddef.h>
 
-#include "decode.hpp"
+#include "decode.hpp"  // launch_xxh3_128_batch
 #include "device_common.hpp"
+#include "host_common.hpp"
 #include "lsmgpu.h"
 
 namespace lsmgpu {

@@ -45,38 +45,9 @@ struct DecodeParams {
   uint32_t huge_tag;      // this call's tag for the huge path's unit-done flags (never 0)
 };
 
-// Diagnostic builds (-DLSM_DIAG, `make variant`) honour ablation bits in
-// lsm_decode_tuning.flags / lsm_block_params.reserved that skip parts of the
-// work (outputs invalid); the release library rejects them (LSM_BAD_ARG).
-#ifdef LSM_DIAG
-constexpr bool kDiagBuild = true;
-#else
-constexpr bool kDiagBuild = false;
-#endif
-constexpr uint32_t kDiagSkipHash = 0x100, kDiagSkipParse = 0x200, kDiagSkipStore = 0x400, kDiagSkipPhaseB = 0x800;
-// (group kernel, stage-only profiling: outputs and statuses invalid) no header / trailer wave; no stage DMA
-constexpr uint32_t kDiagSkipHeader = 0x1000, kDiagSkipDma = 0x2000;
-// (huge-block pool, streamed chains) every chain wave gives up its first wait at once, as the
-// 5 ms no-progress guard would; the fallback chain pass is skipped (LSM_INCOMPLETE stays)
-constexpr uint32_t kDiagStreamGiveUp = 0x4000, kDiagNoChainFallback = 0x8000;
-constexpr uint32_t kDecodeDiagMask = kDiagSkipHash | kDiagSkipParse | kDiagSkipStore | kDiagSkipPhaseB |
-                                     kDiagSkipHeader | kDiagSkipDma | kDiagStreamGiveUp | kDiagNoChainFallback;
-
-// The > 64 KiB dynamic-LDS attribute acts on the CURRENT device: set it once
-// per device (a process may drive several GPUs, one host thread per device).
-inline hipError_t set_lds_attr(const void* fn, uint32_t bytes, uint64_t* done_mask) {
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  const uint64_t bit = dev < 64 ? 1ULL << dev : 0;
-  if (bit && (__atomic_load_n(done_mask, __ATOMIC_ACQUIRE) & bit)) return hipSuccess;
-  e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  if (e == hipSuccess && bit) __atomic_fetch_or(done_mask, bit, __ATOMIC_RELEASE);
-  return e;
-}
-
-// hipSuccess -> LSM_OK; else LSM_HIP_ERROR with the message kept for lsm_last_error().
-int hip_status(hipError_t e, const char* where);
+// The bits of lsm_decode_tuning.flags that a diagnostic build (kDiagBuild) lets through to
+// launch_decode besides the public ones: the ablation bits, one by one in decode_common.hpp.
+constexpr uint32_t kDecodeDiagMask = 0xFF00;
 
 size_t decode_workspace_size(uint32_t n_blocks);
 size_t decode_workspace_size_ex(uint32_t n_blocks, uint64_t blocks_bytes);
@@ -85,6 +56,7 @@ size_t decode_pool_min_bytes(uint32_t n_blocks);
 uint32_t decode_lds_bytes(uint32_t stage_bytes, uint32_t tile_items, uint32_t blocks_per_wave);
 hipError_t launch_decode(const DecodeParams& P, void* workspace, size_t workspace_bytes, hipStream_t st);
 
+// (checksum.hip)
 hipError_t launch_xxh3_128_batch(const uint8_t* data, const uint64_t* off, uint32_t n, uint64_t* out,
                                  hipStream_t st);
 

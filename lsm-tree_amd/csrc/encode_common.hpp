@@ -8,8 +8,8 @@
 #include <type_traits>
 
 #include "block_format.hpp"
-#include "decode.hpp"
 #include "encode.hpp"
+#include "host_common.hpp"
 #include "scan.hpp"
 #include "fill.hpp"
 
@@ -51,7 +51,7 @@ __device__ __host__ __forceinline__ uint32_t bucket_count(uint64_t n, float rati
 }
 
 // EncodeParams::diag (lsm_block_params.reserved, a u8): honoured by diagnostic builds only
-// (kDiagBuild), 0 in normal use.  The decode path's bits are in decode.hpp.
+// (kDiagBuild), 0 in normal use.  The decode path's bits are in decode_common.hpp.
 constexpr uint32_t kDiagNoRecordStores = 1;   // group loop: no record is written to the image
 constexpr uint32_t kDiagNoHash = 2;           // no payload checksum and no header (group loop, listed blocks)
 constexpr uint32_t kDiagNoCopyOut = 4;        // no copy-out of the image (group loop, listed blocks)
@@ -477,29 +477,24 @@ struct EncodeWorkspace {
   size_t wpart;         // u64 [2 per wave of items]
   size_t total;
   EncodeWorkspace(uint64_t n_items, uint32_t n_blocks) {
-    size_t at = 0;
-    auto take = [&at](size_t bytes) {
-      const size_t o = at;
-      at += (bytes + 255) / 256 * 256;
-      return o;
-    };
+    Carver c;
     const size_t nb = n_blocks, ni = (size_t)n_items;
-    kspan = take((nb + 1) * 8);
-    vspan = take((nb + 1) * 8);
-    sizes = take(nb * 8);
-    plans = take(nb * sizeof(BlockPlan));
-    lists = take(nb * 4);
-    counts = take(256);
-    tiles = take(std::max<uint64_t>(scan_tiles(n_blocks), scan_tiles(std::max<uint64_t>(n_items, 1))) * 8);
-    erec = take(ni * 4);
-    hbucket = take(ni * 2);
-    hb_fix = take(256);
-    pfirst = take((nb + 1) * 4);
-    wpart = take((ni / 64 + 1) * 16);
-    total = at;
+    kspan = c.take((nb + 1) * 8);
+    vspan = c.take((nb + 1) * 8);
+    sizes = c.take(nb * 8);
+    plans = c.take(nb * sizeof(BlockPlan));
+    lists = c.take(nb * 4);
+    counts = c.take(256);
+    tiles = c.take(std::max<uint64_t>(scan_tiles(n_blocks), scan_tiles(std::max<uint64_t>(n_items, 1))) * 8);
+    erec = c.take(ni * 4);
+    hbucket = c.take(ni * 2);
+    hb_fix = c.take(256);
+    pfirst = c.take((nb + 1) * 4);
+    wpart = c.take((ni / 64 + 1) * 16);
+    total = c.total();
   }
   // where the whole-GPU E3's pool starts in a workspace that carries one (lsm_encode_workspace_size_ex)
-  size_t pool_base() const { return (total + 255) / 256 * 256; }
+  size_t pool_base() const { return round256(total); }
 };
 
 // ------------------------------------------------------- host: the stage launchers

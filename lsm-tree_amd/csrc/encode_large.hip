@@ -966,14 +966,8 @@ hipError_t launch_encode_large(const EncodeParams& P, hipStream_t st) {
       hipLaunchKernelGGL(encode_huge_plan_kernel, dim3(1), dim3(1024), 0, st, P);
       // one resident wave of record workgroups (no partly filled last wave: 256 KiB encode
       // 0.459 -> 0.424 ms against a 2048-workgroup grid)
-      static int cu_count[64] = {};  // per device (benign race: every writer stores the same count)
-      int dev = 0;
-      if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
-      int n_cu = dev < 64 ? __atomic_load_n(&cu_count[dev], __ATOMIC_RELAXED) : 0;
-      if (!n_cu) {
-        if ((e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-        if (dev < 64) __atomic_store_n(&cu_count[dev], n_cu, __ATOMIC_RELAXED);
-      }
+      int n_cu = 0;
+      if ((e = device_cu_count(&n_cu)) != hipSuccess) return e;
       hipLaunchKernelGGL(encode_huge_records_kernel<kOW>, dim3(kEHugeWgsPerCU * (uint32_t)n_cu), dim3(256), 0, st, P);
       hipLaunchKernelGGL(encode_huge_chain_kernel, dim3(min(P.n_blocks, 1024u)), dim3(256), 0, st, P);
     }

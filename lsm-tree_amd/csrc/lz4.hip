@@ -20,8 +20,8 @@
 #include "fill.hpp"
 
 #include "block_format.hpp"
-#include "decode.hpp"
 #include "device_common.hpp"
+#include "host_common.hpp"
 #include "lsmgpu.h"
 #include "scan.hpp"
 
@@ -333,7 +333,7 @@ __global__ __launch_bounds__(1024) void lz4_cap_kernel(uint64_t* __restrict__ of
 using namespace lsmgpu;
 
 extern "C" size_t lsm_lz4_plan_workspace_size(uint32_t n_blocks) {
-  return ((size_t)n_blocks * 8 + 255) / 256 * 256 + (scan_tiles(n_blocks ? n_blocks : 1) * 8 + 255) / 256 * 256;
+  return round256((size_t)n_blocks * 8) + round256(scan_tiles(n_blocks ? n_blocks : 1) * 8);  // lengths | scan tiles
 }
 
 static int lz4_plan(const uint8_t* d_blocks, const uint64_t* d_block_off, uint32_t n_blocks, uint64_t max_block_bytes,
@@ -344,7 +344,7 @@ static int lz4_plan(const uint8_t* d_blocks, const uint64_t* d_block_off, uint32
     return LSM_BAD_ARG;
   const hipStream_t st = (hipStream_t)stream;
   uint64_t* raw = (uint64_t*)d_workspace;
-  uint64_t* tiles = (uint64_t*)((uint8_t*)d_workspace + ((size_t)n_blocks * 8 + 255) / 256 * 256);
+  uint64_t* tiles = (uint64_t*)((uint8_t*)d_workspace + round256((size_t)n_blocks * 8));
   hipLaunchKernelGGL(lz4_plan_kernel, dim3((n_blocks + 255) / 256), dim3(256), 0, st, d_blocks, d_block_off, n_blocks,
                      max_block_bytes, frame, raw);
   hipError_t e = launch_excl_scan(raw, n_blocks, tiles, Lz4OffOut{d_out_off}, st);

@@ -13,7 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include "block_format.hpp"
-#include "decode.hpp"
+#include "host_common.hpp"
 #include "lsmgpu.h"
 #include "scan.hpp"
 
@@ -151,7 +151,7 @@ using namespace lsmgpu;
 
 extern "C" size_t lsm_materialize_workspace_size(uint64_t n_items) {
   const uint64_t n = n_items ? n_items : 1;
-  return (n * 8 + 255) / 256 * 256 + (scan_tiles(n) * 8 + 255) / 256 * 256;
+  return round256(n * 8) + round256(scan_tiles(n) * 8);  // key lengths | scan tiles
 }
 
 static int mat_params(const uint8_t* d_blocks, const uint64_t* d_block_off, uint32_t n_blocks,
@@ -188,7 +188,7 @@ extern "C" int lsm_materialize_plan(const uint8_t* d_blocks, const uint64_t* d_b
   if (!d_workspace || workspace_bytes < lsm_materialize_workspace_size(n_items)) return LSM_BAD_ARG;
   const hipStream_t st = (hipStream_t)stream;
   P.lens = (uint64_t*)d_workspace;
-  uint64_t* tiles = (uint64_t*)((uint8_t*)d_workspace + (n_items * 8 + 255) / 256 * 256);
+  uint64_t* tiles = (uint64_t*)((uint8_t*)d_workspace + round256(n_items * 8));
   hipError_t e = hipMemsetAsync(P.lens, 0, n_items * 8, st);  // items no block range covers
   if (e != hipSuccess) return hip_status(e, "lsm_materialize_plan");
   if (n_blocks) hipLaunchKernelGGL(key_lengths_kernel, dim3((n_blocks + 3) / 4), dim3(256), 0, st, P);

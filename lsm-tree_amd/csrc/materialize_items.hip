@@ -18,8 +18,8 @@
 #include <hip/hip_runtime.h>
 
 #include "block_format.hpp"
-#include "decode.hpp"
 #include "gather.hpp"
+#include "host_common.hpp"
 #include "lsmgpu.h"
 #include "scan.hpp"
 
@@ -351,15 +351,30 @@ __global__ __launch_bounds__(kMiWaves * 64) void mi_gather_kernel(MiParams P) {
   }
 }
 
-static inline size_t mi_round(uint64_t bytes) { return (bytes + 255) / 256 * 256; }
+// The plan's workspace: byte offsets of its regions, in layout order, and their sum.
+struct MiWorkspace {
+  size_t meta;            // u64 [kMiMeta]
+  size_t klens, vlens;    // u32 [n] each
+  size_t ktiles, vtiles;  // u64 scan tile sums
+  size_t total;
+  explicit MiWorkspace(uint64_t n_items) {
+    const uint64_t n = n_items ? n_items : 1;
+    Carver c;
+    meta = c.take(kMiMeta * 8);
+    klens = c.take(n * 4);
+    vlens = c.take(n * 4);
+    ktiles = c.take(scan_tiles(n) * 8);
+    vtiles = c.take(scan_tiles(n) * 8);
+    total = c.total();
+  }
+};
 
 }  // namespace lsmgpu
 
 using namespace lsmgpu;
 
 extern "C" size_t lsm_materialize_items_workspace_size(uint64_t n_items) {
-  const uint64_t n = n_items ? n_items : 1;
-  return mi_round(kMiMeta * 8) + 2 * mi_round(n * 4) + 2 * mi_round(scan_tiles(n) * 8);
+  return MiWorkspace(n_items).total;
 }
 
 static int mi_params(const uint8_t* d_blocks, const uint64_t* d_block_off, uint32_t n_blocks,
@@ -398,15 +413,16 @@ extern "C" int lsm_materialize_items_plan(const uint8_t* d_blocks, const uint64_
   int rc = mi_params(d_blocks, d_block_off, n_blocks, d_n_blocks, d_item_start, d_status, d_parsed, n_items, d_base, P);
   if (rc != LSM_OK) return rc;
   if (!d_out_key_off || !d_out_val_off || !d_end || !d_result || d_end == d_base) return LSM_BAD_ARG;
-  if (!d_workspace || workspace_bytes < lsm_materialize_items_workspace_size(n_items)) return LSM_BAD_ARG;
+  const MiWorkspace W(n_items);
+  if (!d_workspace || workspace_bytes < W.total) return LSM_BAD_ARG;
   const hipStream_t st = (hipStream_t)stream;
   const uint64_t n = n_items ? n_items : 1;
   uint8_t* ws = (uint8_t*)d_workspace;
-  P.meta = (uint64_t*)ws;
-  P.klens = (uint32_t*)(ws + mi_round(kMiMeta * 8));
-  P.vlens = (uint32_t*)(ws + mi_round(kMiMeta * 8) + mi_round(n * 4));
-  P.ktiles = (uint64_t*)(ws + mi_round(kMiMeta * 8) + 2 * mi_round(n * 4));
-  P.vtiles = (uint64_t*)(ws + mi_round(kMiMeta * 8) + 2 * mi_round(n * 4) + mi_round(scan_tiles(n) * 8));
+  P.meta = (uint64_t*)(ws + W.meta);
+  P.klens = (uint32_t*)(ws + W.klens);
+  P.vlens = (uint32_t*)(ws + W.vlens);
+  P.ktiles = (uint64_t*)(ws + W.ktiles);
+  P.vtiles = (uint64_t*)(ws + W.vtiles);
   P.end = d_end;
   P.out_key_off = d_out_key_off;
   P.out_val_off = d_out_val_off;

@@ -21,9 +21,9 @@
 // (lower bound in higher runs, upper bound in lower runs).
 #include <hip/hip_runtime.h>
 
-#include "decode.hpp"
 #include "device_common.hpp"
 #include "gather.hpp"
+#include "host_common.hpp"
 #include "lsmgpu.h"
 #include "scan.hpp"
 
@@ -355,24 +355,19 @@ struct MergeWorkspace {
   size_t hdr, heads, perm, keep, oidx, klen, vlen, koff, voff, tiles, table, total;
   MergeWorkspace(uint64_t n_items, uint32_t n_runs) {
     const uint64_t n = n_items ? n_items : 1;
-    size_t at = 0;
-    auto take = [&](uint64_t bytes) {
-      const size_t o = at;
-      at += (bytes + 255) / 256 * 256;
-      return o;
-    };
-    hdr = take(sizeof(MergeHdr));
-    heads = take(n * 16);
-    perm = take(n * 4);
-    keep = take(n * 4);
-    oidx = take((n + 1) * 4);
-    klen = take(n * 4);
-    vlen = take(n * 4);
-    koff = take((n + 1) * 8);
-    voff = take((n + 1) * 8);
-    tiles = take(scan_tiles(n + 1) * 8);
-    table = take((n / kMergeSeg + n_runs) * (uint64_t)n_runs * 4);
-    total = at;
+    Carver c;
+    hdr = c.take(sizeof(MergeHdr));
+    heads = c.take(n * 16);
+    perm = c.take(n * 4);
+    keep = c.take(n * 4);
+    oidx = c.take((n + 1) * 4);
+    klen = c.take(n * 4);
+    vlen = c.take(n * 4);
+    koff = c.take((n + 1) * 8);
+    voff = c.take((n + 1) * 8);
+    tiles = c.take(scan_tiles(n + 1) * 8);
+    table = c.take((n / kMergeSeg + n_runs) * (uint64_t)n_runs * 4);
+    total = c.total();
   }
 };
 

@@ -20,7 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include "block_format.hpp"
-#include "decode.hpp"
+#include "host_common.hpp"
 #include "lsmgpu.h"
 
 namespace lsmgpu {

@@ -25,6 +25,7 @@
 #include "fill.hpp"
 
 #include "decode.hpp"
+#include "host_common.hpp"
 #include "lsmgpu.h"
 
 namespace lsmgpu {
@@ -154,8 +155,6 @@ using namespace lsmgpu;
 
 namespace {
 
-constexpr size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-
 // Workspace carve (every level holds at most cap + 1 entries / blocks).
 struct ScanWs {
   uint64_t* h_off;      // index entries: BlockHandle offsets
@@ -171,11 +170,10 @@ struct ScanWs {
 
 size_t scan_ws_size(uint32_t cap, ScanWs* w, uint8_t* base) {
   const size_t e = (size_t)cap + 1;
-  size_t o = 0;
+  Carver c;
   auto take = [&](size_t bytes) {
-    uint8_t* p = base ? base + o : nullptr;
-    o += align256(bytes);
-    return p;
+    const size_t o = c.take(bytes);
+    return base ? base + o : nullptr;
   };
   ScanWs tmp;
   ScanWs& s = w ? *w : tmp;
@@ -188,7 +186,7 @@ size_t scan_ws_size(uint32_t cap, ScanWs* w, uint8_t* base) {
   s.state = (ScanState*)take(sizeof(ScanState));
   s.dec_bytes = decode_workspace_size((uint32_t)e);
   s.dec_ws = take(s.dec_bytes);
-  return o;
+  return c.total();
 }
 
 struct Sync {

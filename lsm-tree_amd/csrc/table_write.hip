@@ -32,10 +32,10 @@
 //                           16 B per lane (gather.hpp), seqnos and handles
 #include <hip/hip_runtime.h>
 
-#include "decode.hpp"
 #include "device_common.hpp"
 #include "fill.hpp"
 #include "gather.hpp"
+#include "host_common.hpp"
 #include "lsmgpu.h"
 #include "scan.hpp"
 
@@ -205,21 +205,16 @@ struct CutWorkspace {
   explicit CutWorkspace(uint64_t n_items) {
     const uint64_t n = n_items ? n_items : 1;
     n_tiles = (uint32_t)((n + kCutTile - 1) / kCutTile);
-    size_t at = 0;
-    auto take = [&](uint64_t bytes) {
-      const size_t o = at;
-      at += (bytes + 255) / 256 * 256;
-      return o;
-    };
-    hdr = take(sizeof(CutHdr));
-    entry1 = take((uint64_t)n_tiles * 4);
-    tcnt = take((uint64_t)n_tiles * 4);
-    clear_end = at;  // hdr, entry1 and tcnt are cleared by every call
-    tbase = take(((uint64_t)n_tiles + 1) * 8);
-    tiles = take(scan_tiles(n_tiles) * 8);
-    jump = take(n * 4);
-    link = take(n * 4);
-    total = at;
+    Carver c;
+    hdr = c.take(sizeof(CutHdr));
+    entry1 = c.take((uint64_t)n_tiles * 4);
+    tcnt = c.take((uint64_t)n_tiles * 4);
+    clear_end = c.total();  // hdr, entry1 and tcnt are cleared by every call
+    tbase = c.take(((uint64_t)n_tiles + 1) * 8);
+    tiles = c.take(scan_tiles(n_tiles) * 8);
+    jump = c.take(n * 4);
+    link = c.take(n * 4);
+    total = c.total();
   }
 };
 
@@ -290,7 +285,16 @@ __global__ __launch_bounds__(kIdxWaves * 64) void index_gather_kernel(IdxParams 
   gather_field(ks, kl, P.out_keys, ko, P.out_key_off[c], P.out_key_off[ce], buf[w], lane);
 }
 
-inline size_t idx_lens_bytes(uint32_t n_blocks) { return ((uint64_t)(n_blocks ? n_blocks : 1) * 4 + 255) / 256 * 256; }
+struct IdxWorkspace {
+  size_t lens, tiles, total;
+  explicit IdxWorkspace(uint32_t n_blocks) {
+    const uint64_t n = n_blocks ? n_blocks : 1;
+    Carver c;
+    lens = c.take(n * 4);
+    tiles = c.take(scan_tiles(n) * 8);
+    total = c.total();
+  }
+};
 
 }  // namespace lsmgpu
 
@@ -340,7 +344,7 @@ extern "C" int lsm_cut_blocks_device(const uint64_t* d_key_off, const uint64_t* 
 }
 
 extern "C" size_t lsm_index_entries_workspace_size(uint32_t n_blocks) {
-  return idx_lens_bytes(n_blocks) + (scan_tiles(n_blocks ? n_blocks : 1) * 8 + 255) / 256 * 256;
+  return IdxWorkspace(n_blocks).total;
 }
 
 extern "C" int lsm_index_entries(const lsm_items* d_items, const uint32_t* d_block_item_start,
@@ -376,8 +380,9 @@ extern "C" int lsm_index_entries(const lsm_items* d_items, const uint32_t* d_blo
   P.out_handle_off = d_out_handle_off;
   P.out_handle_size = d_out_handle_size;
   P.result = d_result;
-  P.lens = (uint32_t*)d_workspace;
-  uint64_t* tiles = (uint64_t*)((uint8_t*)d_workspace + idx_lens_bytes(n_blocks));
+  const IdxWorkspace W(n_blocks);
+  P.lens = (uint32_t*)((uint8_t*)d_workspace + W.lens);
+  uint64_t* tiles = (uint64_t*)((uint8_t*)d_workspace + W.tiles);
   hipLaunchKernelGGL(index_lens_kernel, dim3((n_blocks + 255) / 256), dim3(256), 0, st, P);
   const hipError_t e = launch_excl_scan(P.lens, n_blocks, tiles, IdxOffOut{d_out_key_off}, st);
   if (e != hipSuccess) return hip_status(e, where);

@@ -106,6 +106,38 @@ def test_encode_workspace_sizes_unchanged(L):
                 assert lib.lsm_encode_workspace_size_ex(ni, nb, oc) == want, (ni, nb, oc)
 
 
+def test_workspace_sizes_unchanged(L):
+    """The decode workspace's regions are listed once (DecodeWorkspace, csrc/decode.hip) and the other
+    stages carve theirs with one carver (csrc/host_common.hpp); every size function still returns,
+    over a grid of edge sizes, what the library returned when each summed its regions by hand
+    (tests/golden/workspace_sizes.json: rows of [arguments..., bytes])."""
+    import json
+    lib = L.lib()
+    gold = json.loads((ROOT / "tests" / "golden" / "workspace_sizes.json").read_text())
+    edges = (0, 1, 2047, 2048, 2049, 1 << 20)
+    dec_n = (1, 2, 2047, 2048, 2049, 65536, 1 << 20)
+    # (72 KiB: the general path's stage, 32 KiB: a huge block's work unit)
+    dec_bytes = (0, 8703, 8704, 32767, 32768, 32769, 73727, 73728, 73729, 131072, 1 << 20, 1 << 32)
+    grids = {
+        "lsm_decode_workspace_size": [(n,) for n in dec_n],
+        "lsm_decode_workspace_size_ex": [(n, b) for n in dec_n for b in dec_bytes],
+        "lsm_merge_workspace_size": [(n, r) for n in edges for r in (1, 2, 64)],
+        "lsm_cut_workspace_size": [(n,) for n in edges + (16383, 16384, 16385)],
+        "lsm_index_entries_workspace_size": [(n,) for n in edges],
+        "lsm_materialize_workspace_size": [(n,) for n in edges + (31, 32, 33)],
+        "lsm_materialize_items_workspace_size": [(n,) for n in edges + (63, 64, 65)],
+        "lsm_scan_workspace_size": [(n,) for n in (0, 1, 2046, 2047, 2048, 65536, 1 << 20)],
+        "lsm_lz4_workspace_size": [(n,) for n in edges],
+        "lsm_lz4_plan_workspace_size": [(n,) for n in edges],
+    }
+    assert set(grids) == set(gold) - {"comment"}
+    for name, grid in grids.items():
+        rows = {tuple(r[:-1]): r[-1] for r in gold[name]}
+        assert sorted(rows) == sorted(grid), name
+        for args in grid:
+            assert getattr(lib, name)(*args) == rows[args], (name, args)
+
+
 def test_bad_args_rejected_without_device(L):
     """Argument validation happens before any HIP call."""
     import ctypes as C

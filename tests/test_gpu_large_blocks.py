@@ -377,7 +377,7 @@ def test_huge_encode_concurrent_streams(gpu):
 
 # Diagnostic build (-DLSM_DIAG, lsm-tree_amd/.variants/libdiag.so, built by
 # __graft_entry__.build()): decode flag bits that force the streamed chains'
-# give-up path deterministically (csrc/decode.hpp).
+# give-up path deterministically (csrc/decode_common.hpp).
 DIAG_STREAM_GIVE_UP = 0x4000
 DIAG_NO_CHAIN_FALLBACK = 0x8000
 
