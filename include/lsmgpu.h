@@ -39,6 +39,7 @@
  *   lsm_lz4_plan_output <- the builder_unzeroed(uncompressed_length) sizing of the same  block/mod.rs:104-112
  *   lsm_lz4_plan_framed / lsm_lz4_decompress_framed + lsm_decode_blocks_tuned(LSM_DECODE_PAYLOAD_VERIFIED)
  *                      <- Block::from_reader(Lz4) then DataBlock::new + iter   block/mod.rs:104-118, data_block/mod.rs:335,476
+ *   lsm_lz4_compress_blocks <- Block::write_into with CompressionType::Lz4  block/mod.rs:60-74
  *   lsm_materialize_plan / lsm_materialize_keys <- DataBlockParsedItem::materialize  data_block/mod.rs:296-315
  *   lsm_materialize_items_plan / lsm_materialize_items
  *                      <- the same producing the owned InternalValue (key and value) that Scanner::next
@@ -506,6 +507,50 @@ int lsm_lz4_decompress_framed(const uint8_t* d_blocks, const uint64_t* d_block_o
 int lsm_lz4_plan_capped(const uint8_t* d_blocks, const uint64_t* d_block_off, uint32_t n_blocks,
                         uint64_t max_block_bytes, int framed, uint64_t out_cap, uint64_t* d_out_off,
                         void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ---- LZ4 block compression --------------------------------------------------
+ * Block::write_into(.., CompressionType::Lz4) (block/mod.rs:60-74), batched, as a
+ * stage of its own after lsm_encode_blocks (which keeps writing
+ * CompressionType::None).  Input block b is d_blocks[d_block_off[b] ..
+ * d_block_off[b+1]) = Header(33) || payload exactly as lsm_encode_blocks wrote it
+ * (same buffer rules as lsm_decode_blocks).  Output block b is Header' || the LZ4
+ * block-format stream of the payload, where Header' has the same magic and block
+ * type, data_length = the stream's length, uncompressed_length = the payload's
+ * length, checksum = xxh3_128 of the stream and the header checksum recomputed.
+ * Output blocks are packed back to back from offset 0 of d_out; d_out_off
+ * (n_blocks+1 device u64) receives their offsets and can be handed to
+ * lsm_index_entries as its d_block_off.
+ *  - Always LZ4, also where the stream is longer than the payload (lz4_flex has no
+ *    stored fallback; the compression type belongs to the table).  An empty payload
+ *    gives the one-byte stream 00.
+ *  - The stream is a conforming LZ4 block (offsets 1..65535, matches >= 4 bytes, the
+ *    last sequence literals only, the last 5 bytes literals, no match starting in the
+ *    last 12 bytes), decodable by lz4_flex and liblz4 alike.  Which matches it holds
+ *    is pinned by no format field; it is a pure function of the payload bytes: the
+ *    same payload gives the same stream wherever it sits in the batch.
+ *  - Input checks (the payload is not hashed again): a handle < 33 bytes or
+ *    data_length != size - 33 -> LSM_TRUNCATED, bad magic -> LSM_BAD_MAGIC, type > 3
+ *    -> LSM_BAD_TYPE, data_length != uncompressed_length (already compressed) or a
+ *    payload above LZ4's 0x7E000000 input limit -> LSM_UNSUPPORTED.  d_in_status may
+ *    be NULL, else it is the encoder's d_status: a block whose entry is not LSM_OK gets
+ *    that status.  A rejected block occupies 0 output bytes and leaves its neighbours
+ *    as they are.
+ *  - lsm_lz4_compress_bound(blocks_bytes, n_blocks) is an out_cap that cannot overflow
+ *    (per block 33 + len + len/255 + 16).  A block whose end would pass out_cap gets
+ *    LSM_OVERFLOW and no byte of it is written; d_out_off still holds the real offsets.
+ *  - Workspace: lsm_lz4_compress_workspace_size(n_blocks, blocks_bytes) bytes, 256-byte
+ *    aligned, blocks_bytes = d_block_off[n_blocks] - d_block_off[0].  A block whose
+ *    slot does not fit a workspace sized for fewer bytes gets LSM_BAD_ARG.
+ *  - n_blocks == 0 is a no-op returning LSM_OK; NULL or misaligned buffers or a
+ *    workspace below lsm_lz4_compress_workspace_size(n_blocks, 0) return LSM_BAD_ARG
+ *    before any HIP call.  The call is asynchronous, does no host synchronisation and
+ *    no waiting between workgroups, and can be captured into a graph on one stream. */
+uint64_t lsm_lz4_compress_bound(uint64_t blocks_bytes, uint32_t n_blocks);
+size_t lsm_lz4_compress_workspace_size(uint32_t n_blocks, uint64_t blocks_bytes);
+int lsm_lz4_compress_blocks(const uint8_t* d_blocks, const uint64_t* d_block_off, uint32_t n_blocks,
+                            const int32_t* d_in_status, uint8_t* d_out, uint64_t out_cap,
+                            uint64_t* d_out_off, int32_t* d_status,
+                            void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* ---- materialize (DataBlockParsedItem::materialize, data_block/mod.rs:296-315) --
  * Owned keys of decoded items: key = Slice::fused(prefix, suffix) =

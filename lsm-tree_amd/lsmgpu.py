@@ -256,6 +256,15 @@ def lib():
             L.lsm_index_entries.argtypes = [C.POINTER(LsmItems), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64,
                                             C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        if hasattr(L, "lsm_lz4_compress_blocks"):  # (variant builds of earlier trees lack it: A/B scripts)
+            L.lsm_lz4_compress_bound.restype = C.c_uint64
+            L.lsm_lz4_compress_bound.argtypes = [C.c_uint64, C.c_uint32]
+            L.lsm_lz4_compress_workspace_size.restype = C.c_size_t
+            L.lsm_lz4_compress_workspace_size.argtypes = [C.c_uint32, C.c_uint64]
+            L.lsm_lz4_compress_blocks.restype = C.c_int
+            L.lsm_lz4_compress_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                  C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                  C.c_void_p]
         _lib = L
     return _lib
 
@@ -279,7 +288,8 @@ EXPORTED_SYMBOLS = ["lsm_abi_version", "lsm_status_name", "lsm_last_error", "lsm
                     "lsm_xxh3_128_stream_update_batch", "lsm_xxh3_128_stream_digest_batch",
                     "lsm_merge_workspace_size", "lsm_merge_runs",
                     "lsm_cut_workspace_size", "lsm_cut_blocks_device",
-                    "lsm_index_entries_workspace_size", "lsm_index_entries"]
+                    "lsm_index_entries_workspace_size", "lsm_index_entries",
+                    "lsm_lz4_compress_bound", "lsm_lz4_compress_workspace_size", "lsm_lz4_compress_blocks"]
 
 
 def _check(rc, what):
@@ -774,6 +784,31 @@ def decode_lz4_blocks(blocks, block_off, n_blocks=None, expect_type=-1, item_cap
     return out
 
 
+def lz4_compress_blocks(blocks, block_off, n_blocks=None, in_status=None, out_cap=None, stream=None):
+    """Block::write_into with CompressionType::Lz4 over a batch (block/mod.rs:60-74):
+    blocks = padded uint8 cuda tensor of uncompressed blocks as Encoder.encode wrote them,
+    block_off = int64 cuda [n+1], in_status = the encoder's status (or None).  Each block
+    becomes Header' || LZ4 stream of its payload, packed from offset 0.  out_cap defaults to
+    lsm_lz4_compress_bound of the input buffer, which cannot overflow.  No host
+    synchronisation.  Returns dict(buf: uint8 cuda, padded by LSM_INPUT_PADDING so it feeds
+    decode_lz4_blocks; block_off: int64 cuda [n+1]; status: int32 cuda [n])."""
+    torch = _torch()
+    n = block_off.numel() - 1 if n_blocks is None else n_blocks
+    dev = blocks.device
+    blocks_bytes = blocks.numel()  # (an upper bound of block_off[n] - block_off[0]: no read-back)
+    if out_cap is None:
+        out_cap = int(lib().lsm_lz4_compress_bound(blocks_bytes, n))
+    buf = padded_bytes(out_cap, dev)
+    out_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    ws = torch.empty(lib().lsm_lz4_compress_workspace_size(n, blocks_bytes), dtype=torch.uint8, device=dev)
+    _check(lib().lsm_lz4_compress_blocks(_ptr(blocks), _ptr(block_off), n, _ptr(in_status), _ptr(buf), out_cap,
+                                         _ptr(out_off), _ptr(status), _ptr(ws), ws.numel(), _stream(stream)),
+           "lsm_lz4_compress_blocks")
+    ws.record_stream(torch.cuda.current_stream(dev) if stream is None else stream)
+    return {"buf": buf, "block_off": out_off, "status": status[:n]}
+
+
 def materialize_keys(blocks, block_off, n_blocks, out, n_items=None, stream=None, key_cap=None):
     """DataBlockParsedItem::materialize (data_block/mod.rs:296-315) of decode output `out`
     (dict from decode_blocks / scan_table) -> (keys uint8 cuda arena, key_off int64 cuda
@@ -923,7 +958,7 @@ def index_entries(items, starts, block_off, n_blocks, base_offset=0, key_cap=Non
 
 
 def write_table(items, block_size=4096, restart_interval=16, hash_ratio=0.0, two_level=False, partition_size=4096,
-                handle_overhead=48, n_items=None):
+                handle_overhead=48, n_items=None, compression=None):
     """The data and block-index regions of a table file, built on the device: what
     pyoracle.table_write builds on the host (Writer::write / spill_block, writer/mod.rs:243-343;
     FullIndexWriter::finish, writer/index/full.rs:55-69; PartitionedIndexWriter,
@@ -934,9 +969,16 @@ def write_table(items, block_size=4096, restart_interval=16, hash_ratio=0.0, two
     + handle_overhead), which the reference does not pin; the scan does not depend on where
     partitions are cut.  Only scalars are read back: the block counts, the item count and the
     region ends.  The filter, meta, TOC and trailer regions are not written.
+    compression: None, or "lz4" = the default data_block_compression_policy below level 0
+    (config/mod.rs:275-283): the data blocks are encoded, then compressed
+    (lz4_compress_blocks), and the index is built over the compressed offsets; the index
+    partitions and the TLI stay uncompressed (index_block_compression_policy: None).
     Returns dict(file: uint8 cuda tensor (a view of a padded buffer), tli_off, tli_size,
-    index_off, data_len, block_count, block_off (data blocks, int64 cuda), starts (int32 cuda))."""
+    index_off, data_len, block_count, block_off (data blocks as stored, int64 cuda),
+    starts (int32 cuda), compression)."""
     torch = _torch()
+    if compression not in (None, "lz4"):
+        raise LsmError(f"write_table: compression {compression!r} (None or \"lz4\")")
     dev = items["keys"].device
     starts = cut_blocks_device(items, block_size, n_items=n_items)
     nb = starts.numel() - 1
@@ -959,6 +1001,11 @@ def write_table(items, block_size=4096, restart_interval=16, hash_ratio=0.0, two
         return torch.tensor([0, count], dtype=torch.int32, device=dev)
 
     data, data_len = encode(items, starts, nb, restart_interval=restart_interval, hash_ratio=hash_ratio)
+    if compression == "lz4":
+        data = lz4_compress_blocks(data["buf"], data["block_off"], nb, in_status=data["status"])
+        data_len = int(data["block_off"][nb].item())
+        if not bool((data["status"][:nb] == 0).all().item()):
+            raise LsmError("write_table: a block failed to compress")
     handles = index_entries(items, starts, data["block_off"], nb)
     pieces = [data["buf"][:data_len]]
     index_off = data_len
@@ -978,7 +1025,8 @@ def write_table(items, block_size=4096, restart_interval=16, hash_ratio=0.0, two
     file = padded_bytes(total, dev)
     torch.cat(pieces, out=file[:total])
     return {"file": file[:total], "tli_off": tli_off, "tli_size": tli_size, "index_off": index_off,
-            "data_len": data_len, "block_count": nb, "block_off": data["block_off"][:nb + 1], "starts": starts}
+            "data_len": data_len, "block_count": nb, "block_off": data["block_off"][:nb + 1], "starts": starts,
+            "compression": compression}
 
 
 def items_to_device(items_np, device="cuda", off32=False):
