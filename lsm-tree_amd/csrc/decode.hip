@@ -11,11 +11,11 @@
 // contiguous on disk, so a group is one contiguous span):
 //   1. lane j of every wave holds block j's handle and item range;
 //   2. all waves copy the span HBM -> LDS with global_load_lds_dwordx4;
-//   3. wave 0: lane j checks block j's header fields and trailer, a wave scan
-//      numbers the restart intervals of the group;
-//   4. phase A on one wave (lane = restart interval) walks record boundaries
-//      only, while the other waves verify the payload xxh3_128 (16-lane DPP
-//      rows) and the header checksums;
+//   3. one wave (it rotates with the group): lane j checks block j's header
+//      fields and trailer, a row scan numbers the restart intervals of the group,
+//   4. and the same wave goes on into phase A (lane = restart interval), which
+//      walks record boundaries only, while the other waves verify the payload
+//      xxh3_128 (16-lane DPP rows) and the header checksums from step 2 on;
 //   5. phase B on all waves (thread = record) parses and validates every
 //      field and stores the parsed-item SoA with coalesced global stores.
 // Blocks larger than the stage, index blocks and rare record shapes go to

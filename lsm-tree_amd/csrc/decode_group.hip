@@ -51,6 +51,81 @@ __device__ __forceinline__ Group form_group(const DecodeParams& P, uint32_t b, u
   return G;
 }
 
+// Inclusive scan over lanes 0..15 (one DPP row: a group has at most kMaxGroup = 16 blocks):
+// four row_shr steps, no LDS round trip.  Every lane of the wave must be active.
+static_assert(kMaxGroup <= 16, "the block scan is one 16-lane DPP row");
+__device__ __forceinline__ uint32_t row_incl_scan_u32(uint32_t v) {
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);  // row_shr:1
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);  // row_shr:2
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);  // row_shr:4
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);  // row_shr:8
+  return v;
+}
+
+// Lane-level: one block's header fields and trailer, the checks of meta_header_fields +
+// meta_trailer with the same statuses in the same order, but every load that does not depend
+// on a loaded value issued at once: the trailer lies at a place the handle gives (its last
+// kTrailerLen bytes), so the header words and the trailer words are one LDS round trip and
+// the marker byte before the binary index a second one; the statuses are then selected from
+// the loaded values.  (The helpers return at the first failed check, which makes magic,
+// type, checksum words, trailer words and marker five dependent round trips.)
+// hb / len: the block in the stage (len <= stage bytes); cap: its item capacity.
+__device__ __forceinline__ void group_block_meta(const uint8_t* stage, uint32_t hb, uint32_t len, int32_t expect_type,
+                                                 uint32_t cap, bool compact, BlockMeta& m) {
+  const uint32_t p0 = hb + kHdrLen, plen = len - kHdrLen;
+  const bool has_tr = len >= kHdrLen + kTrailerLen + 1;
+  const uint32_t tp = has_tr ? hb + len - kTrailerLen : hb;  // (no trailer: any address inside the stage)
+  // header and trailer words (reads past a short block stay inside the stage and its pad)
+  const uint32_t magic = read_u32_unaligned(stage, hb);
+  const uint32_t type = read_u32_unaligned(stage, hb + 4) & 0xFF;
+  const BaseReader64 r{stage, hb};
+  m.ck_lo = r(5);
+  m.ck_hi = r(13);
+  const uint32_t data_length = read_u32_unaligned(stage, hb + 21);
+  const uint32_t w0 = read_u32_unaligned(stage, tp);
+  const uint32_t ri = w0 & 0xFF, step = (w0 >> 8) & 0xFF;
+  const uint32_t bin_len = read_u32_unaligned(stage, tp + 2);
+  const uint32_t bin_off = read_u32_unaligned(stage, tp + 6);
+  const uint32_t item_count = read_u32_unaligned(stage, tp + 27);
+  // Header::decode_from order (check_header_fields)
+  const int32_t hst = len < 4                ? (int32_t)ST_TRUNCATED
+                      : magic != 0x034D534CU ? (int32_t)ST_BAD_MAGIC
+                      : len < 5              ? (int32_t)ST_TRUNCATED
+                      : type > 3             ? (int32_t)ST_BAD_TYPE
+                      : len < kHdrLen        ? (int32_t)ST_TRUNCATED
+                                             : (int32_t)ST_OK;
+  // read_trailer's structural checks up to the marker
+  const bool shape_ok = has_tr && ri != 0 && (step == 2 || step == 4) && bin_len != 0 && bin_off != 0 &&
+                        (uint64_t)bin_off + (uint64_t)bin_len * step <= (uint64_t)(plen - kTrailerLen);
+  const uint32_t marker = read_u32_unaligned(stage, shape_ok ? p0 + bin_off - 1 : hb) & 0xFF;
+  // bin_len == ceil(item_count / ri) in 32 bits (bin_len != 0 here, so no items never matches)
+  const bool count_ok = item_count != 0 && (item_count - 1) / (ri ? ri : 1u) + 1 == bin_len;
+  const int32_t tst = !shape_ok || marker != kTrailerMarker || !count_ok || (type == 1 && ri != 1) ? (int32_t)ST_PARSE
+                      : item_count > cap                                                           ? (int32_t)ST_OVERFLOW
+                                                                                                   : (int32_t)ST_OK;
+  // meta_trailer order: data length, expected type, block kinds without items, trailer
+  const int32_t st = hst != ST_OK                                        ? hst
+                     : data_length != plen                               ? (int32_t)ST_TRUNCATED
+                     : (expect_type >= 0 && (int32_t)type != expect_type) ? (int32_t)ST_TYPE_MISMATCH
+                     : type == 2                                         ? (int32_t)ST_UNSUPPORTED
+                     : (compact && (type == 1 || plen > 0xFFFFu))        ? (int32_t)ST_UNSUPPORTED
+                                                                         : tst;
+  const bool ok = st == ST_OK;
+  m.p0 = p0;
+  m.rec_end = ok ? p0 + bin_off - 1 : 0;
+  m.st = st;
+  m.type = type;
+  m.hb = hb;
+  m.len = len;
+  m.ri = ri;
+  m.step = step;
+  m.bin_len = ok ? bin_len : 0;
+  m.bin_off = bin_off;
+  m.item_count = item_count;
+  m.chain0 = 0;
+  m.hdr_st = hst;
+}
+
 #if defined(LSM_DIAG) && !defined(LSM_DIAG_NOTIME)
 // wave 0 per group, role timers summed over waves: entries 16..31
 __device__ unsigned long long g_group_phase[32];
@@ -58,15 +133,24 @@ hipError_t decode_group_phases(uint64_t* sum32) { return take_dec_phases(g_group
 #endif
 
 // Workgroup = kGroupWaves waves sharing one LDS stage (default 32 KiB: eight
-// 4-KiB blocks, ~32 restart intervals).  Per group:
+// 4-KiB blocks, ~32 restart intervals).  Per group, three barriers (DMA landed, phase A and
+// hash done, phase B done):
 //   all waves   LDS-DMA of the span (wave w moves 1-KiB pieces w, w+4, ...)
-//   wave 0      headers + trailers (lane j = block j), interval numbering
-//   wave pa     phase A over all intervals (every lane walks one interval)
-//   other waves payload checksums (16-lane DPP rows, four blocks per wave)
+//   wave pa     headers + trailers (lane j = block j), interval numbering, then phase A
+//               (every lane walks one interval) with no barrier in between: the wave reads
+//               what its own lanes wrote, which a wave-level ordering covers
+//   other waves payload and header checksums (16-lane DPP rows, four blocks per wave), from
+//               the DMA barrier on: a block's place in the stage follows from its handle,
+//               and the verdict is consulted only in the status merge, where a block whose
+//               header failed has its digest ignored
 //   all waves   phase B (thread = record), coalesced SoA stores
 // pa rotates with the group index so the serial walk lands on each SIMD in
 // turn.  Phase A needs only the trailer, not the checksum, so it runs
 // concurrently with the hash; statuses merge in oracle order at the end.
+// A group of more than 64 restart intervals has phase A on up to three waves.  The hash
+// waves cannot know that before the numbering is done, so that path keeps a fourth barrier:
+// wave pa walks its share at once, the others theirs after the hash (the interval total is
+// handed over in the stage pad's last word), and the workgroup meets once more before phase B.
 constexpr uint32_t kGroupWaves = 4;
 // 17-bit record descriptors for stages of 64 KiB and more (two 8-wave workgroups per CU)
 constexpr bool kDecWide = kDefaultStageBytes >= 65536;
@@ -98,6 +182,9 @@ __global__ __launch_bounds__(kGroupWaves * kWave) __attribute__((amdgpu_waves_pe
   // XXH3 long-path secret words in LDS (read per use by the lean row hash).
   const uint32_t slot_stride = ((P.stage_bytes + 15) & ~15u) + kStagePad;
   LongSecret* ls = reinterpret_cast<LongSecret*>(img + slot_stride);
+  // A group's restart-interval total, from the wave that numbers the intervals to the others:
+  // the last 16 bytes of the stage pad (the parsers read at most 138 bytes past a span).
+  uint32_t* const grp_total = reinterpret_cast<uint32_t*>(img + slot_stride - 16);
   if (tid < sizeof(LongSecret) / 8)
     reinterpret_cast<uint64_t*>(ls)[tid] = reinterpret_cast<const uint64_t*>(&kLongSecret)[tid];
   uint32_t iter = 0;
@@ -143,70 +230,86 @@ __global__ __launch_bounds__(kGroupWaves * kWave) __attribute__((amdgpu_waves_pe
     lds_barrier();
     DEC_PHASE(0);
     const Group Gn = next_group(b + k);
-    // ---- 2. wave 0: headers, trailers, restart-interval numbering; owner[c] = block of interval c
-    if (wave == 0 && !(kDiagBuild && (P.flags & kDiagSkipHeader))) {
-      uint32_t chains = 0;
-      BlockMeta m;
-      if ((uint32_t)lane < k) {
-        meta_header_fields(stage, (uint32_t)(G.off_j - G.span0), G.end_j - G.off_j, m);
-        m.item0 = G.it0_j - G.g_item0;
-        m.hdr_st = m.st;
-        m.ck_bad = 0;
-        m.hck_bad = 0;
-        meta_trailer(stage, P.expect_type, G.it1_j - G.it0_j, m, P.compact);
-        if (m.st == ST_OK && m.type == 1) m.st = ST_DEFER;  // index blocks: general path
-        chains = m.st == ST_OK ? m.bin_len : 0;
+    const uint32_t role = (wave + kGroupWaves - iter % kGroupWaves) % kGroupWaves;  // rotates per group
+    // payload checksums (not when verified upstream: the LZ4 path checks the stored bytes)
+    const bool hash = !(kDiagBuild && (P.flags & kDiagSkipHash)) && !(P.flags & LSM_DECODE_PAYLOAD_VERIFIED);
+    // ---- 2. role 0: headers, trailers, numbering, phase A  ||  checksums on the other three waves
+    if (role == 0) {
+      // lane j = block j; owner[c] = block of restart interval c
+      uint32_t total = 0;
+      if (!(kDiagBuild && (P.flags & kDiagSkipHeader))) {
+        uint32_t chains = 0;
+        BlockMeta m;
+        if ((uint32_t)lane < k) {
+          group_block_meta(stage, (uint32_t)(G.off_j - G.span0), (uint32_t)(G.end_j - G.off_j), P.expect_type,
+                           G.it1_j - G.it0_j, P.compact, m);
+          m.item0 = G.it0_j - G.g_item0;
+          if (m.st == ST_OK && m.type == 1) m.st = ST_DEFER;  // index blocks: general path
+          chains = m.st == ST_OK ? m.bin_len : 0;
+        }
+        const uint32_t incl = row_incl_scan_u32(chains);
+        if ((uint32_t)lane < k) {
+          m.chain0 = incl - chains;
+          // all but ck_bad / hck_bad: those two belong to the hash waves, which may have written them already
+          __builtin_memcpy(&meta[lane], &m, offsetof(BlockMeta, ck_bad));
+          for (uint32_t r = 0; r < chains; ++r) owner[m.chain0 + r] = (uint8_t)lane;
+        }
+        total = wave_readlane_u32(incl, k - 1);
       }
-      const uint32_t incl = wave_incl_scan_u32(chains);
-      if ((uint32_t)lane < k) {
-        m.chain0 = incl - chains;
-        meta[lane] = m;
-        for (uint32_t r = 0; r < chains; ++r) owner[m.chain0 + r] = (uint8_t)lane;
-      }
-    }
-    lds_barrier();
-    DEC_PHASE(1);
-    // ---- 3. phase A on nA waves (64 intervals each)  ||  payload checksums on the others
-    {
-      const uint32_t total = (kDiagBuild && (P.flags & kDiagSkipParse)) ? 0
-                             : meta[k - 1].chain0 + (meta[k - 1].st == ST_OK ? meta[k - 1].bin_len : 0);
-      const uint32_t nA = min((total + kWave - 1) / kWave, kGroupWaves - 1);
-      const uint32_t role = (wave + kGroupWaves - iter % kGroupWaves) % kGroupWaves;  // rotates per group
-      // payload checksums (not when verified upstream: the LZ4 path checks the stored bytes)
-      const bool hash = !(kDiagBuild && (P.flags & kDiagSkipHash)) && !(P.flags & LSM_DECODE_PAYLOAD_VERIFIED);
-      if (role < nA) {
-        phase_a<kDecWide>(stage, meta, owner, rec, role * kWave, nA * kWave, total, P.tile_items);
+      if (kDiagBuild && (P.flags & kDiagSkipParse)) total = 0;
+      if (lane == 0) *grp_total = total;
+      wave_sync();  // meta and owner: written and read by this wave alone until the barrier
+      DEC_ROLE(14);
+      // its share of phase A (all of it up to 64 intervals)
+      if (total) {
+        const uint32_t nA = min((total + kWave - 1) / kWave, kGroupWaves - 1);
+        phase_a<kDecWide>(stage, meta, owner, rec, 0, nA * kWave, total, P.tile_items);
         DEC_ROLE(8);
-      } else if (hash && (k <= kGroupWaves - nA || (k <= (kGroupWaves - nA) * 4 && (role - nA) * 4 + 1 == k))) {
+      }
+    } else if (hash) {
+      // Block jb of the group lies at hb_j of lane jb, len_j bytes (a handle shorter than a
+      // header has no checksums to compare: its header status is final).  The expected
+      // digest is read from the header bytes here; ck_bad / hck_bad are read after the
+      // next barriers, in the status merge, and only for blocks whose header fields passed.
+      const uint32_t hb_j = (uint32_t)(G.off_j - G.span0), len_j = (uint32_t)(G.end_j - G.off_j);
+      const uint32_t hw = kGroupWaves - 1, hr = role - 1;  // three hash waves, this one's index
+      if (k <= hw || (k <= hw * 4 && hr * 4 + 1 == k)) {
         // few (large) blocks: one wave per block, the 64-lane XXH3 (1 KiB per
         // step); also a wave whose share of the rows below is one block
         // (k = 4 h + 1, e.g. nine 4 KiB blocks on three hash waves): the whole
         // wave hashes it instead of one row with three rows idle
-        const uint32_t jb = k <= kGroupWaves - nA ? role - nA : k - 1;
-        if (jb < k && meta[jb].hdr_st == ST_OK) {
-          const uint32_t hb = meta[jb].hb, plen = meta[jb].len - kHdrLen;
-          uint64_t lo, hi;
-          xxh3_128_wave(stage, hb + kHdrLen, plen, ls, lo, hi);
-          const bool hck = header_cksum_ok(stage, hb);
-          if (lane == 0) {
-            meta[jb].ck_bad = lo != meta[jb].ck_lo || hi != meta[jb].ck_hi;
-            meta[jb].hck_bad = !hck;
+        const uint32_t jb = k <= hw ? hr : k - 1;
+        if (jb < k) {
+          const uint32_t hb = wave_readlane_u32(hb_j, jb), len = wave_readlane_u32(len_j, jb);
+          if (len >= kHdrLen) {
+            uint64_t lo, hi;
+            xxh3_128_wave(stage, hb + kHdrLen, len - kHdrLen, ls, lo, hi);
+            const bool hck = header_cksum_ok(stage, hb);
+            if (lane == 0) {
+              const BaseReader64 r{stage, hb};
+              meta[jb].ck_bad = lo != r(5) || hi != r(13);
+              meta[jb].hck_bad = !hck;
+            }
           }
         }
         DEC_ROLE(10);
-      } else if (hash) {
-        const uint32_t rows = (kGroupWaves - nA) * 4;
-        for (uint32_t jb = (role - nA) * 4 + (lane >> 4); jb < k; jb += rows) {
-          if (meta[jb].hdr_st != ST_OK) continue;
-          const uint32_t hb = meta[jb].hb, len = meta[jb].len;
-          uint64_t lo, hi;
-          const uint32_t plen = len - kHdrLen;
-          if (plen > 240) xxh3_128_row_long_lean(stage, hb + kHdrLen, plen, ls, lo, hi);
-          else xxh3_128_short(plen, BaseReader8{stage, hb + kHdrLen}, BaseReader64{stage, hb + kHdrLen}, lo, hi);
-          const bool hck = header_cksum_ok(stage, hb);
-          if ((lane & 15) == 0) {
-            meta[jb].ck_bad = lo != meta[jb].ck_lo || hi != meta[jb].ck_hi;
-            meta[jb].hck_bad = !hck;
+      } else {
+        const uint32_t rows = hw * 4;
+        for (uint32_t j0 = 0; j0 < k; j0 += rows) {  // wave-uniform: the shuffles run with every lane active
+          const uint32_t jb = j0 + hr * 4 + (lane >> 4);
+          const uint32_t hb = (uint32_t)__shfl((int)hb_j, (int)min(jb, kWave - 1u));
+          const uint32_t len = (uint32_t)__shfl((int)len_j, (int)min(jb, kWave - 1u));
+          if (jb < k && len >= kHdrLen) {
+            uint64_t lo, hi;
+            const uint32_t plen = len - kHdrLen;
+            if (plen > 240) xxh3_128_row_long_lean(stage, hb + kHdrLen, plen, ls, lo, hi);
+            else xxh3_128_short(plen, BaseReader8{stage, hb + kHdrLen}, BaseReader64{stage, hb + kHdrLen}, lo, hi);
+            const bool hck = header_cksum_ok(stage, hb);
+            if ((lane & 15) == 0) {
+              const BaseReader64 r{stage, hb};
+              meta[jb].ck_bad = lo != r(5) || hi != r(13);
+              meta[jb].hck_bad = !hck;
+            }
           }
         }
         DEC_ROLE(12);
@@ -214,22 +317,36 @@ __global__ __launch_bounds__(kGroupWaves * kWave) __attribute__((amdgpu_waves_pe
     }
     lds_barrier();
     DEC_PHASE(2);
+    // ---- 3. more than 64 intervals: the other phase-A waves' shares, and the barrier this path keeps
+    {
+      const uint32_t total = *grp_total;  // the same for every wave: written before the barrier above
+      const uint32_t nA = min((total + kWave - 1) / kWave, kGroupWaves - 1);
+      if (nA > 1) {
+        if (role != 0 && role < nA) {
+          phase_a<kDecWide>(stage, meta, owner, rec, role * kWave, nA * kWave, total, P.tile_items);
+          DEC_ROLE(8);
+        }
+        lds_barrier();
+        DEC_PHASE(1);
+      }
+    }
     // ---- 4. phase B: thread = record; full parse + validation; coalesced stores
     if (!(kDiagBuild && (P.flags & (kDiagSkipParse | kDiagSkipPhaseB))))
       phase_b<kAllFields, kCompact, kDecWide>(P, stage, meta, rec, G.n_items, G.g_item0, threadIdx.x, blockDim.x);
     lds_barrier();
     DEC_PHASE(3);
     // refill the stage after phase B, before wave 0's status merge (which reads
-    // only meta): 0.2-0.8 % faster than after it over five batch shapes
+    // only meta, after the barriers behind every writer of it): 0.2-0.8 % faster
+    // than after it over five batch shapes
     if (Gn.k) issue_dma(Gn, img);
     if (wave == 0) {
       int32_t st = ST_OK;
       if ((uint32_t)lane < k) {
         const BlockMeta& m = meta[lane];
         st = m.hdr_st != ST_OK ? m.hdr_st
-             : m.hck_bad ? (int32_t)ST_HDR_CKSUM
-             : m.ck_bad  ? (int32_t)ST_CKSUM
-                         : m.st;
+             : (hash && m.hck_bad) ? (int32_t)ST_HDR_CKSUM  // (no hash: nobody wrote the two verdicts)
+             : (hash && m.ck_bad)  ? (int32_t)ST_CKSUM
+                                   : m.st;
         if (st != ST_DEFER) gstore(P.status, b + lane, st);
       }
       defer_blocks_wave(P, (uint32_t)lane < k && st == ST_DEFER, b + lane);

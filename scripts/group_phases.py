@@ -3,7 +3,11 @@
 diagnostic build: LSMGPU_LIB=lsm-tree_amd/.variants/libdiag.so) on the
 configs[1] shape, configs[3] (16 KiB prefix) and the configs[4] 4/16 KiB
 segments. Ticks are per group, wave 0 for the barrier phases; the role rows
-are the mean over the waves that ran that role."""
+are the mean over the waves that ran that role.  The header / trailer step runs
+on the phase-A wave with no barrier after it: its own time is the "role header"
+row, "role phase A" on that wave counts from the DMA barrier (header included),
+and the "more phase A" phase is the extra barrier interval of groups with more
+than 64 restart intervals (zero otherwise)."""
 import ctypes as C
 import sys
 from pathlib import Path
@@ -44,9 +48,9 @@ for name, nb, kw in CASES:
     groups = max(1, g[5])
     print(f"{name}: {nb} blocks, {ms:.3f} ms, {groups} groups ({g[6] / groups:.2f} blocks/group); "
           f"big kernel blocks {buf[15]}")
-    for i, nm in enumerate(["wait DMA", "header/trailer", "phase A | hash", "phase B", "status + next DMA"]):
-        print(f"  {nm:20s} {g[i] / groups:9.0f}")
-    for i, nm in ((8, "role phase A"), (10, "role hash (wave/block)"), (12, "role hash (rows)")):
+    for i, nm in enumerate(["wait DMA", "more phase A", "header, phase A | hash", "phase B", "status + next DMA"]):
+        print(f"  {nm:24s} {g[i] / groups:9.0f}")
+    for i, nm in ((14, "role header"), (8, "role phase A"), (10, "role hash (wave/block)"), (12, "role hash (rows)")):
         c = max(1, g[i + 1])
         print(f"  {nm:24s} {g[i] / c:9.0f}  x{g[i + 1] / groups:.2f} per group")
     del items, enc, out
