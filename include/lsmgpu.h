@@ -47,6 +47,10 @@
  *   lsm_scan_table     <- Scanner::new / next      src/table/scanner.rs:24-92 (block handles from the
  *                         block index: FullBlockIndex / TwoLevelBlockIndex, src/table/block_index/,
  *                         regions from the TOC, src/table/regions.rs:55-76)
+ *   lsm_table_get      <- Table::get / point_read  src/table/mod.rs:229-340 (seqno-range check, filter
+ *                         block, BlockIndex::forward_reader over FullBlockIndex / TwoLevelBlockIndex,
+ *                         index_block::Iter::seek index_block/iter.rs:25-34, load_data_block +
+ *                         DataBlock::point_read)
  *   lsm_merge_runs     <- Merger::new / next       src/merge.rs:34-100
  *                         CompactionStream          src/compaction/stream.rs:46-221
  *                         InternalKey Ord           src/key.rs:59-72
@@ -691,6 +695,73 @@ int lsm_scan_table_async(const uint8_t* d_file, uint64_t file_len, const lsm_tab
                          uint32_t data_blocks_hint, const lsm_parsed_items* d_out, uint64_t item_cap, uint32_t* d_item_start, int32_t* d_status,
                          uint32_t* d_n_blocks, int32_t* d_table_status, void* d_workspace, size_t workspace_bytes,
                          void* stream);
+
+/* ---- point lookup in a table (Table::get, src/table/mod.rs:229-340) -----------
+ * Batched Table::get(key, seqno, key_hash) on one table file image d_file[0 .. file_len)
+ * (same buffer rules as lsm_scan_table): the block index is searched on the device, so
+ * the caller names no data block.  table: tli_off, tli_size, two_level and global_seqno
+ * as for lsm_scan_table (block_count is ignored).  filter_off / filter_size: the region
+ * handle of the TOC's "filter" section, a block Header ‖ Bloom image of type
+ * LSM_BLOCK_FILTER, never compressed (mod.rs:257,271); filter_size == 0 = the table
+ * has no filter.  lowest_seqno: metadata.seqnos.0.  Needles and snapshots as
+ * lsm_point_read_blocks (arena 16-byte aligned, readable LSM_INPUT_PADDING bytes past
+ * its end).  d_key_hash: xxh3_64 of each needle, as Tree::get computes it once for every
+ * table (NULL: the kernel hashes the needle, and only when there is a filter).
+ * d_active: NULL = every query; else a query with d_active[q] == 0 is not processed and
+ * none of its outputs is written, so a caller can walk several tables newest first
+ * without a host round trip.
+ * Per query, in the reference's order:
+ *  1. snap' = d_snapshot[q] saturating-minus global_seqno; lowest_seqno >= snap' gives
+ *     LSM_GET_SEQNO_SKIP (mod.rs:239-243);
+ *  2. with a filter: the filter block's header fields and the image header are checked,
+ *     contains_hash false gives LSM_GET_FILTERED (mod.rs:280-289);
+ *  3. the index seek (index_block/iter.rs:25-34 over Decoder::seek(pred, true),
+ *     block/decoder.rs:210-304): the first entry whose (end_key, seqno) fails
+ *     end_key < needle || (end_key == needle && seqno >= snap'), by binary search over the
+ *     block's binary index (2- or 4-byte steps; index blocks have restart interval 1, any
+ *     other value is LSM_PARSE).  Full index (block_index/full.rs:23-30): no such entry
+ *     gives LSM_GET_NO_BLOCK.  Two-level (block_index/two_level.rs:110-173): the same seek
+ *     in the TLI, then in every partition from there on, handles yielded in order across
+ *     partitions; a partition whose seek finds nothing ends the iteration;
+ *  4. for each yielded handle (mod.rs:317-340): DataBlock::point_read with snap'; a hit
+ *     gives LSM_GET_HIT; a miss where the handle's end key is greater than the needle gives
+ *     LSM_GET_MISS; otherwise the next handle.  Handles exhausted: LSM_GET_MISS if a block
+ *     was read, else LSM_GET_NO_BLOCK.
+ * Outputs: d_out as lsm_point_read_blocks (item required; item = index of the hit in its
+ * block, -1 for every non-hit; seqno = the item's seqno + global_seqno, wrapping as
+ * lsm_scan_table; val_off / val_len relative to the block's payload), d_hit_block_off /
+ * d_hit_block_size (either may be NULL) = the handle of the answering block, so the value
+ * is file[block_off + 33 + val_off ..); d_outcome (may be NULL) = LSM_GET_*;
+ * d_status[q] = LSM_OK for outcomes 1-5, else the error at which the reference's get
+ * returns Err (outcome LSM_GET_NONE): LSM_BAD_MAGIC / LSM_BAD_TYPE / LSM_TRUNCATED from a
+ * block header; LSM_TYPE_MISMATCH (TLI or partition not Index, data block not Data, filter
+ * not Filter); LSM_PARSE (trailer or record malformed); LSM_TRUNCATED (a handle shorter than
+ * a header or ending past file_len, or data_length != size - 33); LSM_UNSUPPORTED (a data or
+ * index block with data_length != uncompressed_length, i.e. an LZ4 table, or a Bloom
+ * k > LSM_BLOOM_MAX_K); LSM_BAD_MAGIC for a malformed Bloom image header.
+ * Limits: partitioned filters (the TOC's "filter_tli") are not supported (the reference
+ * leaves the unpinned form unimplemented, mod.rs:265-266); LZ4-compressed tables are not
+ * supported.  Payload checksums are not recomputed (the contract of
+ * lsm_point_read_blocks: blocks as loaded by Block::from_file): verify the regions once
+ * with lsm_decode_blocks or lsm_xxh3_128_batch.  No byte outside
+ * d_file[0 .. file_len + LSM_INPUT_PADDING) is read, whatever the file holds.
+ * Asynchronous on `stream`: no host synchronisation, no workspace.
+ * LSM_BAD_ARG (before any device work): a NULL required pointer, d_file or d_needles not
+ * 16-byte aligned, tli_size < 33, the TLI or the filter range outside the file. */
+enum {
+    LSM_GET_NONE = 0,       /* d_status[q] != LSM_OK */
+    LSM_GET_SEQNO_SKIP = 1, /* the table holds nothing below the snapshot */
+    LSM_GET_FILTERED = 2,   /* the Bloom filter excludes the key */
+    LSM_GET_NO_BLOCK = 3,   /* the index names no block for the key */
+    LSM_GET_MISS = 4,       /* a data block was read, no visible version in it */
+    LSM_GET_HIT = 5
+};
+int lsm_table_get(const uint8_t* d_file, uint64_t file_len, const lsm_table_scan* table,
+                  uint64_t filter_off, uint32_t filter_size, uint64_t lowest_seqno,
+                  const uint8_t* d_needles, const uint64_t* d_needle_off, const uint64_t* d_snapshot,
+                  const uint64_t* d_key_hash, const uint8_t* d_active, uint32_t n_queries,
+                  const lsm_point_result* d_out, uint64_t* d_hit_block_off, uint32_t* d_hit_block_size,
+                  uint8_t* d_outcome, int32_t* d_status, void* stream);
 
 /* ---- merge of sorted runs with compaction GC ----------------------------------
  * CompactionStream::new(Merger::new(runs), gc_seqno_threshold)

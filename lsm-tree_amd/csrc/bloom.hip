@@ -18,18 +18,11 @@
 // the probe latency bound; neither is an HBM-streaming kernel.
 #include <hip/hip_runtime.h>
 
-#include "device_common.hpp"
+#include "bloom.hpp"
 #include "host_common.hpp"
 #include "lsmgpu.h"
 
 namespace lsmgpu {
-
-constexpr uint32_t kBloomHdr = 22;  // magic 4 + filter type 1 + hash type 1 + m u64 + k u64
-constexpr uint64_t kBloomMaxK = LSM_BLOOM_MAX_K;
-
-__device__ __forceinline__ uint64_t bloom_secondary(uint64_t h1) {  // builder.rs:10-13
-  return (h1 >> 32) * 0x517cc1b727220a95ULL;
-}
 
 __global__ __launch_bounds__(256) void hash64_keys_kernel(const uint8_t* __restrict__ keys,
                                                           const uint64_t* __restrict__ key_off, uint64_t n,
@@ -77,32 +70,14 @@ __global__ __launch_bounds__(256) void bloom_contains_kernel(const uint8_t* __re
   const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
   // StandardBloomFilterReader::new (mod.rs:36-86), re-read by every lane from one cached line
-  uint64_t m = 0, k = 0;
-#pragma unroll
-  for (int b = 7; b >= 0; --b) {
-    m = (m << 8) | filter[6 + b];
-    k = (k << 8) | filter[14 + b];
-  }
-  const bool ok = filter[0] == 'L' && filter[1] == 'S' && filter[2] == 'M' && filter[3] == 3 && filter[4] == 0 &&
-                  filter[5] == 0 && m > 0 && (m + 7) / 8 <= len - kBloomHdr &&
+  uint64_t m, k;
+  const bool ok = bloom_read_header(filter, len, m, k) &&
                   k <= kBloomMaxK;  // bounded probe loop (a garbage k must not spin a wave)
   if (!ok) {
     out[j] = LSM_BLOOM_BAD_FILTER;
     return;
   }
-  const uint8_t* bits = filter + kBloomHdr;
-  uint64_t h1 = hashes[j], h2 = bloom_secondary(h1);
-  uint8_t r = 1;
-  for (uint64_t i = 1; i <= k; ++i) {
-    const uint64_t idx = h1 % m;
-    if (!(bits[idx >> 3] & (0x80u >> (idx & 7)))) {
-      r = 0;
-      break;
-    }
-    h1 += h2;
-    h2 *= i;
-  }
-  out[j] = r;
+  out[j] = bloom_probe(filter + kBloomHdr, m, k, hashes[j]) ? 1 : 0;
 }
 
 static inline uint32_t grid_for(uint64_t n) { return (uint32_t)((n + 255) / 256); }

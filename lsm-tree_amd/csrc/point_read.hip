@@ -19,8 +19,8 @@
 // checked structurally, the payload checksum is not re-computed.
 #include <hip/hip_runtime.h>
 
-#include "block_format.hpp"
 #include "host_common.hpp"
+#include "point_read.hpp"
 #include "lsmgpu.h"
 
 namespace lsmgpu {
@@ -37,44 +37,6 @@ struct PointReadParams {
   lsm_point_result out;
   int32_t* status;
 };
-
-__device__ __forceinline__ uint32_t win_byte(const Win16& w, uint32_t i) {
-  return (uint32_t)((i < 8 ? w.lo >> (8 * i) : w.hi >> (8 * (i - 8))) & 0xFF);
-}
-
-// Lexicographic compare of a[ap .. ap+an) with b[bp .. bp+bn) (both bases
-// 4-byte aligned, 16-byte windows; both spans readable up to 20 bytes past).
-__device__ __forceinline__ int cmp_span(const uint8_t* ab, uint32_t ap, uint32_t an, const uint8_t* bb, uint32_t bp,
-                                        uint32_t bn) {
-  const uint32_t n = min(an, bn);
-  for (uint32_t k = 0; k < n; k += 16) {
-    const Win16 wa = read_win16(ab, ap + k), wb = read_win16(bb, bp + k);
-    const uint32_t m = min(16u, n - k);
-    uint64_t x0 = wa.lo ^ wb.lo, x1 = wa.hi ^ wb.hi;
-    if (m < 8) {
-      x0 &= (1ULL << (8 * m)) - 1;
-      x1 = 0;
-    } else if (m < 16) {
-      x1 &= m == 8 ? 0ULL : (1ULL << (8 * (m - 8))) - 1;
-    }
-    if (x0 | x1) {
-      const uint32_t i = x0 ? (uint32_t)__builtin_ctzll(x0) >> 3 : 8 + ((uint32_t)__builtin_ctzll(x1) >> 3);
-      return win_byte(wa, i) < win_byte(wb, i) ? -1 : 1;
-    }
-  }
-  return an < bn ? -1 : (an > bn ? 1 : 0);
-}
-
-// compare_prefixed_slice(prefix, suffix, needle), src/table/util.rs:133-167.
-__device__ __forceinline__ int cmp_prefixed(const uint8_t* kb, uint32_t pre, uint32_t pn, uint32_t suf, uint32_t sn,
-                                            const uint8_t* nb, uint32_t np, uint32_t nn) {
-  if (nn == 0) return (pn + sn) > 0 ? 1 : 0;
-  const uint32_t m = min(pn, nn);
-  const int c = cmp_span(kb, pre, m, nb, np, m);
-  if (c) return c;
-  if (pn > nn) return 1;
-  return cmp_span(kb, suf, sn, nb, np + pn, nn - pn);
-}
 
 __global__ __launch_bounds__(256) void point_read_kernel(PointReadParams P) {
   const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -104,67 +66,7 @@ __global__ __launch_bounds__(256) void point_read_kernel(PointReadParams P) {
   TrailerInfo t;
   const uint32_t p0 = hb + kHdrLen;
   if (st == ST_OK) st = read_trailer(base, p0, h.data_length, t);
-  if (st == ST_OK) {
-    bool search = true, miss = false;
-    uint32_t start = 0;
-    if (t.hash_len > 0) {
-      if ((uint64_t)t.hash_off + t.hash_len > (uint64_t)h.data_length - kTrailerLen) {  // bucket bytes precede the trailer
-        st = ST_PARSE;
-      } else {
-        const uint64_t hv = xxh3_64_any(nn, BaseReader8{nb, np}, BaseReader64{nb, np});
-        const uint32_t m = read_u32_unaligned(base, p0 + t.hash_off + (uint32_t)(hv % t.hash_len)) & 0xFF;
-        if (m == kHashFree) {
-          miss = true;
-        } else if (m != kHashConflict) {
-          if (m >= t.bin_len) st = ST_PARSE;
-          start = m;
-          search = false;
-        }
-      }
-    }
-    if (st == ST_OK && !miss && search) {  // last restart head with key < needle
-      uint32_t lo = 0, hi = t.bin_len;
-      while (lo < hi && st == ST_OK) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        Cursor c;
-        c.init(base, p0, bin_get(base, p0, t, mid), t.rec_end);
-        ItemFields f;
-        if (!parse_data_record(c, true, 0, f)) {
-          st = ST_PARSE;
-          break;
-        }
-        if (cmp_span(base, p0 + f.key_off, f.key_len, nb, np, nn) < 0) lo = mid + 1;
-        else hi = mid;
-      }
-      start = lo == 0 ? 0 : lo - 1;
-    }
-    if (st == ST_OK && !miss) {  // linear scan from restart head `start`
-      Cursor c;
-      c.init(base, p0, bin_get(base, p0, t, start), t.rec_end);
-      uint32_t head_key = 0;
-      for (uint64_t i = (uint64_t)start * t.ri; i < t.item_count; ++i) {
-        const bool restart = i % t.ri == 0;
-        ItemFields f;
-        if (!parse_data_record(c, restart, head_key, f)) {
-          st = ST_PARSE;
-          break;
-        }
-        int cmp;
-        if (restart) {
-          head_key = f.key_off;
-          cmp = cmp_span(base, p0 + f.key_off, f.key_len, nb, np, nn);
-        } else {
-          cmp = cmp_prefixed(base, p0 + head_key, f.prefix_len, p0 + f.key_off, f.key_len, nb, np, nn);
-        }
-        if (cmp > 0) break;
-        if (cmp < 0) continue;
-        if (f.seqno >= snap) continue;
-        found = (int64_t)i;
-        hit = f;
-        break;
-      }
-    }
-  }
+  if (st == ST_OK) st = point_read_block(base, p0, h.data_length, t, nb, np, nn, snap, found, hit);
   P.status[q] = st;
   P.out.item[q] = st == ST_OK ? (int32_t)found : -1;
   if (found >= 0) {

@@ -208,6 +208,12 @@ def lib():
         L.lsm_scan_table.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(LsmTableScan), C.c_void_p, C.c_uint32,
                                      C.POINTER(LsmParsed), C.c_uint64, C.c_void_p, C.c_void_p,
                                      C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.c_void_p, C.c_size_t, C.c_void_p]
+        if hasattr(L, "lsm_table_get"):  # (variant builds of earlier trees lack it: A/B scripts)
+            L.lsm_table_get.restype = C.c_int
+            L.lsm_table_get.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(LsmTableScan), C.c_uint64, C.c_uint32,
+                                        C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_uint32, C.POINTER(LsmPointResult), C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]
         L.lsm_materialize_workspace_size.restype = C.c_size_t
         L.lsm_materialize_workspace_size.argtypes = [C.c_uint64]
         L.lsm_materialize_plan.restype = C.c_int
@@ -289,7 +295,8 @@ EXPORTED_SYMBOLS = ["lsm_abi_version", "lsm_status_name", "lsm_last_error", "lsm
                     "lsm_merge_workspace_size", "lsm_merge_runs",
                     "lsm_cut_workspace_size", "lsm_cut_blocks_device",
                     "lsm_index_entries_workspace_size", "lsm_index_entries",
-                    "lsm_lz4_compress_bound", "lsm_lz4_compress_workspace_size", "lsm_lz4_compress_blocks"]
+                    "lsm_lz4_compress_bound", "lsm_lz4_compress_workspace_size", "lsm_lz4_compress_blocks",
+                    "lsm_table_get"]
 
 
 def _check(rc, what):
@@ -516,6 +523,41 @@ def point_read(blocks, block_off, n_blocks, query_block, needles, needle_off, sn
     _check(lib().lsm_point_read_blocks(_ptr(blocks), _ptr(block_off), n_blocks, _ptr(query_block), _ptr(needles),
                                        _ptr(needle_off), _ptr(snapshot), n, C.byref(res), _ptr(out["status"]),
                                        _stream(stream)), "lsm_point_read_blocks")
+    return out
+
+
+GET_NONE, GET_SEQNO_SKIP, GET_FILTERED, GET_NO_BLOCK, GET_MISS, GET_HIT = range(6)
+TABLE_GET_FIELDS = (("item", "int32"), ("seqno", "int64"), ("val_off", "int32"), ("val_len", "int32"),
+                    ("vtype", "uint8"), ("block_off", "int64"), ("block_size", "int32"), ("outcome", "uint8"),
+                    ("status", "int32"))
+
+
+def table_get(file, table, needles, needle_off, snapshot, key_hash=None, active=None, filter=None, lowest_seqno=0,
+              global_seqno=0, stream=None, out=None):
+    """Batched Table::get (src/table/mod.rs:229-340) on a table file image: file = padded uint8
+    cuda tensor; table = dict with tli_off, tli_size, two_level (write_table's result with
+    two_level added; an optional file_len, else the end of the TLI / filter region); needles uint8
+    (padded arena), needle_off int64 [n+1], snapshot int64 [n]; key_hash int64 [n] (xxh3_64 of each
+    needle) or None; active uint8 [n] or None; filter = (off, size) of the filter block or None.
+    Returns dict of cuda tensors item/seqno/val_off/val_len/vtype/block_off/block_size/outcome
+    (GET_*)/status; item -1 = no hit, the value of a hit is
+    file[block_off + 33 + val_off : ... + val_len].  out: such a dict to write into (rows of
+    inactive queries keep what it holds), e.g. the result of the previous, newer table.
+    No host synchronisation."""
+    torch = _torch()
+    n = int(snapshot.numel())
+    dev = file.device
+    if out is None:
+        out = {f: torch.zeros(max(n, 1), dtype=getattr(torch, dt), device=dev) for f, dt in TABLE_GET_FIELDS}
+    f_off, f_size = filter if filter is not None else (0, 0)
+    file_len = table.get("file_len", max(table["tli_off"] + table["tli_size"], f_off + f_size))
+    t = LsmTableScan(table["tli_off"], table["tli_size"], int(bool(table.get("two_level", False))),
+                     global_seqno & (2 ** 64 - 1), 0)
+    res = LsmPointResult(*(_ptr(out[f]) for f in ("item", "seqno", "val_off", "val_len", "vtype")))
+    _check(lib().lsm_table_get(_ptr(file), file_len, C.byref(t), f_off, f_size, lowest_seqno, _ptr(needles),
+                               _ptr(needle_off), _ptr(snapshot), _ptr(key_hash), _ptr(active), n, C.byref(res),
+                               _ptr(out["block_off"]), _ptr(out["block_size"]), _ptr(out["outcome"]),
+                               _ptr(out["status"]), _stream(stream)), "lsm_table_get")
     return out
 
 
