@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "lsmgpu.h"
+
 namespace lsmgpu {
 
 // Diagnostic builds (-DLSM_DIAG, `make variant`) honour ablation bits in
@@ -45,6 +47,16 @@ inline hipError_t device_cu_count(int* n_cu) {
     if (dev < 64) __atomic_store_n(&cu_count[dev], *n_cu, __ATOMIC_RELAXED);
   }
   return hipSuccess;
+}
+
+// The block handle (off, size) holds a header and lies in a file of file_len
+// bytes: the test of both handle kernels of table_scan.hip and, on the TLI's
+// handle, of the tables' entry points (load_block of table_get.hip spells it out).
+__host__ __device__ inline bool handle_in_file(uint64_t off, uint32_t size, uint64_t file_len) {
+  return size >= LSM_HEADER_LEN && off + size >= off && off + size <= file_len;
+}
+inline bool tli_in_file(const lsm_table_scan& table, uint64_t file_len) {
+  return handle_in_file(table.tli_off, table.tli_size, file_len);
 }
 
 // Workspace regions are 256-byte aligned.

@@ -71,10 +71,16 @@ struct LoadedBlock {
 
 // load_block (src/table/util.rs:79-86) without the payload checksum (the caller
 // verifies regions once): the handle lies in the file, header fields, block
-// type, uncompressed, trailer.  index: an index block (restart interval 1).
+// type, extent, uncompressed, trailer.  index: an index block (restart interval 1).
+// The type is tested before the extent, as the reference does (it decodes the
+// header, compares the block type and only then reads data_length bytes);
+// point_read_kernel and seek_kernel (point_read.hip) are given the extent by
+// their caller and test it first (TRUNCATED), then the type (TYPE_MISMATCH).
+// The order decides the status of a block with both faults and is pinned by
+// tests/test_gpu_lookup_status.py; do not unify the two.
 __device__ __forceinline__ int32_t load_block(const TableGetParams& P, uint64_t off, uint32_t size, uint32_t type,
                                               LoadedBlock& b) {
-  if (size < kHdrLen || off + size < off || off + size > P.file_len) return ST_TRUNCATED;
+  if (size < kHdrLen || off + size < off || off + size > P.file_len) return ST_TRUNCATED;  // (handle_in_file)
   b.base = P.file + (off & ~15ULL);
   const uint32_t hb = (uint32_t)(off & 15);
   HeaderInfo h;
@@ -234,9 +240,7 @@ extern "C" int lsm_table_get(const uint8_t* d_file, uint64_t file_len, const lsm
     return LSM_BAD_ARG;
   // the kernel reads the file and the needles through aligned 4-byte windows from 16-byte-aligned bases
   if (((uintptr_t)d_file & 15) || ((uintptr_t)d_needles & 15)) return LSM_BAD_ARG;
-  if (table->two_level > 1 || table->tli_size < LSM_HEADER_LEN || table->tli_off + table->tli_size < table->tli_off ||
-      table->tli_off + table->tli_size > file_len)
-    return LSM_BAD_ARG;
+  if (table->two_level > 1 || !lsmgpu::tli_in_file(*table, file_len)) return LSM_BAD_ARG;
   if (filter_size && (filter_off + filter_size < filter_off || filter_off + filter_size > file_len)) return LSM_BAD_ARG;
   lsmgpu::TableGetParams P{d_file, file_len, table->tli_off, table->tli_size, table->two_level, table->global_seqno,
                            filter_off, filter_size, lowest_seqno, d_needles, d_needle_off, d_snapshot, d_key_hash,

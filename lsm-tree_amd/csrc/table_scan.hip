@@ -20,7 +20,8 @@
 // general path).  lsm_scan_table reads each level's entry count back to size
 // the next launch (one stream synchronisation per index level);
 // lsm_scan_table_async keeps the counts on the device and launches each level
-// for the caller's bounds.
+// for the caller's bounds.  Here: the handle kernels, the two walks and their
+// DecodeParams; "a handle lies in the file" is host_common.hpp's.
 #include <hip/hip_runtime.h>
 #include "fill.hpp"
 
@@ -29,6 +30,18 @@
 #include "lsmgpu.h"
 
 namespace lsmgpu {
+
+// Entry i of a level's n handles is sound: it holds a header and lies in the
+// file (handle_in_file, host_common.hpp), the first starts at first_at (~0:
+// anywhere), and entry i + 1 starts where it ends.
+__device__ __forceinline__ bool handle_ok(const uint64_t* __restrict__ h_off, const uint32_t* __restrict__ h_size,
+                                          uint32_t i, uint32_t n, uint64_t file_len, uint64_t first_at) {
+  const uint64_t o = h_off[i];
+  bool ok = handle_in_file(o, h_size[i], file_len);
+  if (i == 0) ok = ok && (first_at == ~0ULL || o == first_at);
+  if (i + 1 < n) ok = ok && h_off[i + 1] == o + h_size[i];
+  return ok;
+}
 
 // Handles of one index level -> block offsets for lsm_decode_blocks (n+1
 // entries).  bad[0] = the first entry whose handle does not start where the
@@ -41,14 +54,9 @@ __global__ __launch_bounds__(256) void handles_to_offsets_kernel(const uint64_t*
                                                                  uint32_t* __restrict__ bad) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const uint64_t o = h_off[i], sz = h_size[i];
-  const uint64_t e = o + sz;
-  bool ok = sz >= 33 && e >= o && e <= file_len;
-  if (i == 0) ok = ok && (first_at == ~0ULL || o == first_at);
-  if (i + 1 < n) ok = ok && h_off[i + 1] == e;
-  block_off[i] = o;
-  if (i + 1 == n) block_off[n] = e;
-  if (!ok) atomicMin(bad, i);
+  block_off[i] = h_off[i];
+  if (i + 1 == n) block_off[n] = h_off[i] + h_size[i];
+  if (!handle_ok(h_off, h_size, i, n, file_len, first_at)) atomicMin(bad, i);
 }
 
 // First failing block of a level: bad[0] = min index with status != OK.
@@ -121,13 +129,8 @@ __global__ __launch_bounds__(256) void scan_handles_kernel(const ScanState* st, 
       block_off[i] = h_off[n - 1] + h_size[n - 1];
       continue;
     }
-    const uint64_t o = h_off[i], sz = h_size[i];
-    const uint64_t e = o + sz;
-    bool ok = sz >= 33 && e >= o && e <= file_len;
-    if (i == 0) ok = ok && (first_at == ~0ULL || o == first_at);
-    if (i + 1 < n) ok = ok && h_off[i + 1] == e;
-    block_off[i] = o;
-    if (!ok) atomicMin(bad, i);
+    block_off[i] = h_off[i];
+    if (!handle_ok(h_off, h_size, i, n, file_len, first_at)) atomicMin(bad, i);
   }
 }
 
@@ -201,22 +204,37 @@ struct Sync {
   }
 };
 
-DecodeParams index_params(const uint8_t* file, const uint64_t* off, uint32_t n, const ScanWs& w, uint32_t cap) {
+// What every level's decode shares: its ranges, where its counts and statuses go, the default tuning.
+DecodeParams level_params(const uint8_t* file, const uint64_t* off, uint32_t n, uint32_t type, uint32_t* item_start,
+                          int32_t* status) {
   DecodeParams P{};
   P.blocks = file;
   P.block_off = off;
   P.n_blocks = n;
-  P.expect_type = LSM_BLOCK_INDEX;
-  P.out.handle_off = w.h_off;
-  P.out.val_len = w.h_size;  // index blocks: val_len = BlockHandle size
-  P.item_cap = cap;
-  P.item_start = P.item_start_w = w.lvl_start;
-  P.status = w.lvl_status;
+  P.expect_type = type;
+  P.item_start = P.item_start_w = item_start;
+  P.status = status;
   P.blocks_per_wave = kDefaultBlocksPerWave;
   P.stage_bytes = kDefaultStageBytes;
   P.tile_items = kDefaultTileItems;
-  P.flags = 0;
-  P.seqno_add = 0;
+  return P;
+}
+
+DecodeParams index_params(const uint8_t* file, const uint64_t* off, uint32_t n, const ScanWs& w, uint32_t cap) {
+  DecodeParams P = level_params(file, off, n, LSM_BLOCK_INDEX, w.lvl_start, w.lvl_status);
+  P.out.handle_off = w.h_off;
+  P.out.val_len = w.h_size;  // index blocks: val_len = BlockHandle size
+  P.item_cap = cap;
+  return P;
+}
+
+// The data blocks: one decode pass over n ranges, global_seqno added to every item.
+DecodeParams data_params(const uint8_t* file, const uint64_t* off, uint32_t n, const lsm_table_scan& table,
+                         const lsm_parsed_items& out, uint64_t item_cap, uint32_t* item_start, int32_t* status) {
+  DecodeParams P = level_params(file, off, n, LSM_BLOCK_DATA, item_start, status);
+  P.out = out;
+  P.item_cap = item_cap > 0xFFFFFFFFULL ? 0xFFFFFFFFULL : item_cap;
+  P.seqno_add = table.global_seqno;
   return P;
 }
 
@@ -239,7 +257,7 @@ extern "C" int lsm_scan_table(const uint8_t* d_file, uint64_t file_len, const ls
   scan_ws_size(cap_blocks, &w, (uint8_t*)d_workspace);
   Sync sy{st};
   auto fail = [&](hipError_t e) { return hip_status(e, "lsm_scan_table"); };
-  if (table->tli_size < 33 || table->tli_off + table->tli_size > file_len || table->tli_off + table->tli_size < table->tli_off) {
+  if (!tli_in_file(*table, file_len)) {
     *table_status = LSM_TRUNCATED;
     return LSM_OK;
   }
@@ -287,21 +305,7 @@ extern "C" int lsm_scan_table(const uint8_t* d_file, uint64_t file_len, const ls
     return LSM_OK;
   }
   *n_blocks = n_lvl;
-  // the data blocks: one decode pass, global_seqno added to every item
-  DecodeParams P{};
-  P.blocks = d_file;
-  P.block_off = d_block_off;
-  P.n_blocks = n_lvl;
-  P.expect_type = LSM_BLOCK_DATA;
-  P.out = *d_out;
-  P.item_cap = item_cap > 0xFFFFFFFFULL ? 0xFFFFFFFFULL : item_cap;
-  P.item_start = P.item_start_w = d_item_start;
-  P.status = d_status;
-  P.blocks_per_wave = kDefaultBlocksPerWave;
-  P.stage_bytes = kDefaultStageBytes;
-  P.tile_items = kDefaultTileItems;
-  P.flags = 0;
-  P.seqno_add = table->global_seqno;
+  const DecodeParams P = data_params(d_file, d_block_off, n_lvl, *table, *d_out, item_cap, d_item_start, d_status);
   hipError_t e = launch_decode(P, w.dec_ws, w.dec_bytes, st);
   return e == hipSuccess ? LSM_OK : fail(e);
 }
@@ -322,8 +326,7 @@ extern "C" int lsm_scan_table_async(const uint8_t* d_file, uint64_t file_len, co
   ScanWs w;
   scan_ws_size(cap_blocks, &w, (uint8_t*)d_workspace);
   auto fail = [&](hipError_t e) { return hip_status(e, "lsm_scan_table_async"); };
-  const bool tli_ok = table->tli_size >= 33 && table->tli_off + table->tli_size <= file_len &&
-                      table->tli_off + table->tli_size >= table->tli_off;
+  const bool tli_ok = tli_in_file(*table, file_len);
   ScanState s0{1, tli_ok ? (int32_t)LSM_OK : (int32_t)LSM_TRUNCATED, tli_ok ? 0u : 1u, 0};
   hipError_t e = hipMemcpyAsync(w.state, &s0, sizeof(s0), hipMemcpyHostToDevice, st);
   if (e != hipSuccess) return fail(e);
@@ -349,21 +352,9 @@ extern "C" int lsm_scan_table_async(const uint8_t* d_file, uint64_t file_len, co
     hipLaunchKernelGGL(scan_handles_fail_kernel, dim3(1), dim3(256), 0, st, w.state, w.flag, last, dst);
   }
   hipLaunchKernelGGL(scan_result_kernel, dim3(1), dim3(1), 0, st, w.state, d_n_blocks, d_table_status);
-  // the data blocks: the hint (or the cap) ranges, those past the real count empty
-  DecodeParams P{};
-  P.blocks = d_file;
-  P.block_off = d_block_off;
-  P.n_blocks = data_blocks_hint ? data_blocks_hint : cap_blocks;
-  P.expect_type = LSM_BLOCK_DATA;
-  P.out = *d_out;
-  P.item_cap = item_cap > 0xFFFFFFFFULL ? 0xFFFFFFFFULL : item_cap;
-  P.item_start = P.item_start_w = d_item_start;
-  P.status = d_status;
-  P.blocks_per_wave = kDefaultBlocksPerWave;
-  P.stage_bytes = kDefaultStageBytes;
-  P.tile_items = kDefaultTileItems;
-  P.flags = 0;
-  P.seqno_add = table->global_seqno;
+  // the hint (or the cap) ranges, those past the real count empty
+  const DecodeParams P = data_params(d_file, d_block_off, data_blocks_hint ? data_blocks_hint : cap_blocks, *table,
+                                     *d_out, item_cap, d_item_start, d_status);
   e = launch_decode(P, w.dec_ws, w.dec_bytes, st);
   return e == hipSuccess ? LSM_OK : fail(e);
 }

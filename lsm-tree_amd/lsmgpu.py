@@ -505,6 +505,11 @@ def xxh3_128_batch(data, off, n):
     return out
 
 
+def _point_result(out):
+    """The LsmPointResult over an output dict's item/seqno/val_off/val_len/vtype tensors."""
+    return LsmPointResult(*(_ptr(out[f]) for f in ("item", "seqno", "val_off", "val_len", "vtype")))
+
+
 def point_read(blocks, block_off, n_blocks, query_block, needles, needle_off, snapshot, stream=None):
     """Batched DataBlock::point_read (data_block/mod.rs:412-472).  All inputs cuda
     tensors: blocks uint8 (padded), block_off int64 [n_blocks+1], query_block
@@ -519,7 +524,7 @@ def point_read(blocks, block_off, n_blocks, query_block, needles, needle_off, sn
            "val_len": torch.zeros(max(n, 1), dtype=torch.int32, device=dev),
            "vtype": torch.zeros(max(n, 1), dtype=torch.uint8, device=dev),
            "status": torch.empty(max(n, 1), dtype=torch.int32, device=dev)}
-    res = LsmPointResult(*(_ptr(out[f]) for f in ("item", "seqno", "val_off", "val_len", "vtype")))
+    res = _point_result(out)
     _check(lib().lsm_point_read_blocks(_ptr(blocks), _ptr(block_off), n_blocks, _ptr(query_block), _ptr(needles),
                                        _ptr(needle_off), _ptr(snapshot), n, C.byref(res), _ptr(out["status"]),
                                        _stream(stream)), "lsm_point_read_blocks")
@@ -553,7 +558,7 @@ def table_get(file, table, needles, needle_off, snapshot, key_hash=None, active=
     file_len = table.get("file_len", max(table["tli_off"] + table["tli_size"], f_off + f_size))
     t = LsmTableScan(table["tli_off"], table["tli_size"], int(bool(table.get("two_level", False))),
                      global_seqno & (2 ** 64 - 1), 0)
-    res = LsmPointResult(*(_ptr(out[f]) for f in ("item", "seqno", "val_off", "val_len", "vtype")))
+    res = _point_result(out)
     _check(lib().lsm_table_get(_ptr(file), file_len, C.byref(t), f_off, f_size, lowest_seqno, _ptr(needles),
                                _ptr(needle_off), _ptr(snapshot), _ptr(key_hash), _ptr(active), n, C.byref(res),
                                _ptr(out["block_off"]), _ptr(out["block_size"]), _ptr(out["outcome"]),

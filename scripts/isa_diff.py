@@ -7,7 +7,7 @@ Each side is one or more gfx950 `.s` files (hipcc -save-temps, `make asm`).  Eve
 and the device functions they call) is matched by name; its `.amdhsa_*` resource directives and its
 instruction stream are compared, with local labels (.LBB*, .Ltmp*, ...) masked, so that a function
 may move between translation units.  A function that one side has in several units is compared in
-each.  Prints one line per function (resources and instruction count, a / b) and exits 1 if any
+each, against the other side's copy in the unit of the same name where there is one.  Prints one line per function (resources and instruction count, a / b) and exits 1 if any
 differs or is missing."""
 import argparse
 import re
@@ -86,16 +86,19 @@ def main():
             bad += 1
             print(f"{pretty[n][:86]:86s} only in {'a' if fa else 'b'}")
             continue
-        for _, a in fa[:1]:
-            for pb, b in fb:
-                same_res, same_ins = a["res"] == b["res"], a["ins"] == b["ins"]
-                cell = [f"{a['res'].get(k, '-')}/{b['res'].get(k, '-')}" for k in RES[:4]]
-                verdict = "identical" if same_res and same_ins else ("RESOURCES DIFFER" if not same_res else "code differs")
-                bad += verdict != "identical"
-                kind = "kernel" if a["res"] else "func"
-                where = "" if len(fb) == 1 else f"  [{pb.rsplit('/', 1)[-1]}]"
-                print(f"{pretty[n][:86]:86s} {kind:6s} {cell[0]:>9s} {cell[1]:>9s} {cell[2]:>9s} {cell[3]:>13s} "
-                      f"{len(a['ins']):>6d}/{len(b['ins']):<6d}  {verdict}{where}")
+        unit_a = {pa.rsplit("/", 1)[-1]: a for pa, a in fa}
+        for pb, b in fb:
+            # a function both sides have in the same unit is compared there: a __noinline__ callee is
+            # specialised to the callers of its unit, so its copies differ between units of one build
+            a = unit_a.get(pb.rsplit("/", 1)[-1], fa[0][1])
+            same_res, same_ins = a["res"] == b["res"], a["ins"] == b["ins"]
+            cell = [f"{a['res'].get(k, '-')}/{b['res'].get(k, '-')}" for k in RES[:4]]
+            verdict = "identical" if same_res and same_ins else ("RESOURCES DIFFER" if not same_res else "code differs")
+            bad += verdict != "identical"
+            kind = "kernel" if a["res"] else "func"
+            where = "" if len(fb) == 1 else f"  [{pb.rsplit('/', 1)[-1]}]"
+            print(f"{pretty[n][:86]:86s} {kind:6s} {cell[0]:>9s} {cell[1]:>9s} {cell[2]:>9s} {cell[3]:>13s} "
+                  f"{len(a['ins']):>6d}/{len(b['ins']):<6d}  {verdict}{where}")
     print(f"{len(names)} functions, {bad} differ or are missing")
     return 1 if bad else 0
 
