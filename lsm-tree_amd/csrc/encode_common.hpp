@@ -18,7 +18,9 @@ namespace lsmgpu {
 // Block classes: blocks that fit the group kernel's budget (group_fits) are
 // written by encode_group_kernel; the others are listed by the size scan and
 // written, by the LDS image they need (e2_need), by 1-wave workgroups with a
-// 20 KiB (medium) or 96 KiB (big) image, or straight in HBM (E3, huge).
+// 20 KiB image (medium), by workgroups of kListBigWaves waves with a 96 KiB
+// image (big), or straight in HBM (E3, huge).  plan_block (encode_plan.hpp)
+// is where a block gets its class.
 constexpr uint32_t kPlanHuge = 1, kPlanBad = 2, kPlanMedium = 4, kPlanBig = 8;
 constexpr uint32_t kPlanHugeGpu = 16;  // a huge block the whole-GPU E3 path took over (not the one-workgroup E3)
 constexpr uint32_t kImgMedium = 20 * 1024;

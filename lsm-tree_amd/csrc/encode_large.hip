@@ -205,132 +205,149 @@ struct RecordCopy {
   }
 };
 
-// Block tail in the image: marker, hash-index bytes, trailer, then the fused
-// xxh3_128 + header, and one coalesced 16 B/lane copy-out to the block's
-// place in the packed output.
-__device__ __forceinline__ void finish_block_lds(const EncodeParams& P, uint32_t b, const BlockPlan& pl, uint32_t n,
-                                                 uint32_t ri, uint8_t* img, const uint32_t* hlo, const uint32_t* hhi,
-                                                 uint32_t pad, uint32_t total, uint8_t* gdst) {
-  const int lane = threadIdx.x & 63;
-  const uint32_t step = pl.step_flags & 0xFF;
-  const uint32_t plen = total - kHdrLen, p0 = pad + kHdrLen, bin_off = pl.recs + 1;
-  if (lane == 0) img[p0 + pl.recs] = kTrailerMarker;
-  const uint32_t hash_off = pl.hash_w ? bin_off + pl.bin_len * step : 0;
-  for (uint32_t k = lane; k < pl.hash_w; k += kWave) img[p0 + hash_off + k] = (uint8_t)bucket_byte(hlo[k], hhi[k]);
-  write_trailer_bytes(img, p0 + plen - kTrailerLen, ri, step, pl.bin_len, bin_off, pl.hash_w, hash_off, n);
-  wave_lds_sync();
-  if (!(kDiagBuild && (P.diag & kDiagNoHash))) {
-    uint64_t ck_lo, ck_hi;
-    xxh3_128_wave(img, p0, plen, &kLongSecret, ck_lo, ck_hi);
-    write_header_bytes(img, pad, P.type, ck_lo, ck_hi, plen);
+// ------------------------------------------- the stages of a listed / huge block
+// Where a block's parts lie.  The block is assembled in an image whose byte 0 is 16-byte aligned:
+// an LDS image that is copied out to gdst, or gdst itself (the huge blocks, straight in HBM).
+struct ListedGeom {
+  uint32_t s, n;               // first item, items
+  uint32_t ri, step;           // restart interval, bytes per binary-index entry
+  uint32_t total, plen;        // block bytes with and without the header
+  uint32_t pad, p0;            // image offsets of the header and of the payload
+  uint32_t bin_off, hash_off;  // payload offsets of the binary index and of the hash index (0: none)
+  uint8_t* gdst;               // the block's place in the output, rounded down to 16 bytes
+  bool overflow;               // the block ends past out_cap: nothing of it is written
+};
+__device__ __forceinline__ ListedGeom listed_geom(const EncodeParams& P, const BlockPlan& pl, uint32_t s, uint32_t n,
+                                                  uint64_t dst_off, uint32_t total, bool overflow) {
+  ListedGeom g;
+  g.s = s;
+  g.n = n;
+  g.ri = is_index(P) ? 1 : P.ri;
+  g.step = pl.step_flags & 0xFF;
+  g.total = total;
+  g.plen = total - kHdrLen;
+  const uint64_t dabs = (uint64_t)(uintptr_t)P.out + dst_off;
+  g.pad = (uint32_t)(dabs & 15);
+  g.p0 = g.pad + kHdrLen;
+  g.bin_off = pl.recs + 1;
+  g.hash_off = pl.hash_w ? g.bin_off + pl.bin_len * g.step : 0;
+  g.gdst = reinterpret_cast<uint8_t*>(dabs & ~15ULL);
+  g.overflow = overflow;
+  return g;
+}
+// Block b with plan pl, from the batch's offsets.
+__device__ __forceinline__ ListedGeom listed_geom(const EncodeParams& P, uint32_t b, const BlockPlan& pl) {
+  const uint32_t s = P.starts[b], e = P.starts[b + 1];
+  const uint64_t dst_off = P.block_off[b], dst_end = P.block_off[b + 1];
+  return listed_geom(P, pl, s, e - s, dst_off, (uint32_t)(dst_end - dst_off), dst_end > P.out_cap);
+}
+
+// A block the whole-GPU E3 accepted (it ends inside the output: encode_huge_plan_kernel).
+__device__ __forceinline__ ListedGeom listed_geom(const EncodeParams& P, const EncHuge& h, const BlockPlan& pl) {
+  return listed_geom(P, pl, h.s, h.n, h.dst_off, h.total, false);
+}
+
+// Exclusive prefix of rec over the workgroup's kWaves * 64 threads, in thread order, and the sum.
+// One barrier, behind the psum stores: a caller that scans again puts its own behind the use.
+template <uint32_t kWaves>
+__device__ __forceinline__ uint32_t wg_excl_scan(uint32_t rec, uint32_t* psum, uint32_t* total) {
+  const uint32_t incl = wave_incl_scan_u32(rec);
+  if constexpr (kWaves == 1) {  // the wave scan alone (psum is not used)
+    *total = wave_bcast_u32(incl, kWave - 1);
+    return incl - rec;
+  } else {
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+    if ((threadIdx.x & (kWave - 1)) == kWave - 1) psum[wave] = incl;
+    __syncthreads();
+    // (two loops, not one with a select per wave: with that form the 8-wave listed writer took 173
+    // VGPRs and ran 0.35 % slower than with its own copy of the scan, with this one 157 and 0.5 %
+    // faster, profiles/encode_large_refactor_ab.txt)
+    uint32_t base = 0, tot = 0;
+    for (uint32_t w = 0; w < kWaves; ++w) tot += psum[w];
+    for (uint32_t w = 0; w < wave; ++w) base += psum[w];
+    *total = tot;
+    return base + incl - rec;
   }
-  wave_lds_sync();
-  const uint32_t chunks = (kDiagBuild && (P.diag & kDiagNoCopyOut)) ? 0 : (pad + total + 15) >> 4;
-  for (uint32_t c = lane; c < chunks; c += kWave) {
+}
+
+// The barrier between the stages of a kLW-wave block writer.
+template <uint32_t kLW>
+__device__ __forceinline__ void writer_sync() {
+  if constexpr (kLW == 1) wave_lds_sync();
+  else __syncthreads();
+}
+
+// Hash index of a block whose image is in HBM: the votes of all n keys in LDS passes of
+// kE3HashChunk buckets (hlo / hhi), each pass's bytes to img.  Every thread of the kThreads calls it.
+template <uint32_t kThreads, int kOW>
+__device__ __forceinline__ void hash_index_passes(const EncodeParams& P, uint32_t s, uint32_t n, uint32_t ri,
+                                                  uint32_t hash_w, uint8_t* img, uint32_t p0, uint32_t hash_off,
+                                                  uint32_t* hlo, uint32_t* hhi) {
+  const uint32_t tid = threadIdx.x;
+  for (uint32_t base = 0; base < hash_w; base += kE3HashChunk) {
+    const uint32_t lim = min(kE3HashChunk, hash_w - base);
+    for (uint32_t k = tid; k < lim; k += kThreads) {
+      hlo[k] = 0xFFFFFFFFu;
+      hhi[k] = 0;
+    }
+    __syncthreads();
+    for (uint32_t j = tid; j < n; j += kThreads) {
+      const uint64_t i = (uint64_t)s + j;
+      const uint64_t ko = koff<kOW>(P, i);
+      const uint32_t bk = key_bucket(P, ko, (uint32_t)(koff<kOW>(P, i + 1) - ko), hash_w);
+      if (bk >= base && bk < base + lim) {
+        atomicMin(&hlo[bk - base], j / ri);
+        atomicMax(&hhi[bk - base], j / ri);
+      }
+    }
+    __syncthreads();
+    for (uint32_t k = tid; k < lim; k += kThreads) img[p0 + hash_off + base + k] = (uint8_t)bucket_byte(hlo[k], hhi[k]);
+    __syncthreads();
+  }
+}
+
+// Image bytes [pad, pad + total) to gdst in 16-byte pieces, the ragged first and last piece by bytes.
+template <uint32_t kThreads>
+__device__ __forceinline__ void copy_out_image(const uint8_t* img, uint8_t* gdst, uint32_t pad, uint32_t total) {
+  const uint32_t chunks = (pad + total + 15) >> 4;
+  for (uint32_t c = threadIdx.x; c < chunks; c += kThreads) {
     const uint32_t lo = c * 16, hi = lo + 16;
     if (lo >= pad && hi <= pad + total) {
-      // streaming output: non-temporal (measured 2 % faster than a plain store)
       copy_store16(reinterpret_cast<u32x4*>(gdst) + c, reinterpret_cast<const u32x4*>(img)[c]);
     } else {
       for (uint32_t k = max(lo, pad); k < min(hi, pad + total); ++k) gdst[k] = img[k];
     }
   }
-  if (lane == 0) P.status[b] = ST_OK;
 }
 
-// Listed block b (any item count) assembled by one wave in the LDS image at
-// `smem` (16-B aligned, at least e2_need bytes); shared prefixes and the plan
-// come from the fused pass.
-template <int kOW>
-__device__ __forceinline__ void write_block_lds(const EncodeParams& P, uint32_t b, uint8_t* smem) {
-  const int lane = threadIdx.x & 63;
-  const uint32_t s = P.starts[b], e = P.starts[b + 1];
-  const uint64_t dst_off = P.block_off[b], dst_end = P.block_off[b + 1];
-  const BlockPlan pl = P.plans[b];
-  const uint32_t step = pl.step_flags & 0xFF;
-  if (dst_end > P.out_cap) {
-    if (lane == 0) P.status[b] = ST_OVERFLOW;
-    return;
-  }
-  const uint32_t n = e - s;
-  const uint32_t ri = is_index(P) ? 1 : P.ri;
-  const uint32_t total = (uint32_t)(dst_end - dst_off);
-  const uint64_t dabs = (uint64_t)(uintptr_t)P.out + dst_off;
-  const uint32_t pad = (uint32_t)(dabs & 15);
-  uint8_t* img = smem;
-  uint32_t* hlo = reinterpret_cast<uint32_t*>(smem + ((pad + total + 15) & ~15u) + 32);
-  uint32_t* hhi = hlo + ((pl.hash_w + 3) & ~3u);
-  for (uint32_t k = lane; k < pl.hash_w; k += kWave) {
-    hlo[k] = 0xFFFFFFFFu;
-    hhi[k] = 0;
-  }
-  wave_lds_sync();
-  const uint32_t p0 = pad + kHdrLen;
-  const uint32_t bin_off = pl.recs + 1;
-  uint32_t carry = 0;
-  for (uint32_t c = 0; c < n; c += kWave) {
-    const uint32_t j = c + lane;
-    const bool head = j % ri == 0;
-    ItemMeta m;
-    RecordCopy rc;
-    uint32_t rec = 0;
-    if (j < n) {
-      bool bad = false;
-      m = load_item_lcp<kOW>(P, s, j, ri, bad);
-      rec = (uint32_t)item_record_len(P, m, head);
-    }
-    const uint32_t incl = wave_incl_scan_u32(rec);
-    const uint32_t roff = carry + incl - rec;
-    if (j < n) {
-      rc.issue(P, m, head, p0 + roff);
-      rc.store(P, m, head, img);
-      if (head) store_le(img, p0 + bin_off + (j / ri) * step, roff, step);
-      if (pl.hash_w) {
-        const uint32_t bk = key_bucket(P, m.ko, m.klen, pl.hash_w);
-        atomicMin(&hlo[bk], j / ri);
-        atomicMax(&hhi[bk], j / ri);
-      }
-    }
-    carry += wave_bcast_u32(incl, 63);
-  }
-  wave_lds_sync();
-  finish_block_lds(P, b, pl, n, ri, img, hlo, hhi, pad, total, reinterpret_cast<uint8_t*>(dabs & ~15ULL));
-}
-
-// The same block with every wave of a kLW-wave workgroup: items in chunks of
-// kLW * 64 (workgroup scan), then marker / hash-index bytes / trailer, the
-// payload xxh3_128 (per-KiB contributions on every wave into `contrib`, the
-// scramble chain and the merge on wave 0), the header and the copy-out.  One
-// wave per 20-96 KiB block ran the 64 KiB classes at 0.18 TB/s.
+// Listed block b (any item count) by the kLW waves of a workgroup, assembled in the LDS image at
+// `smem` (16-B aligned, at least e2_need bytes) and copied out to its place in the packed output:
+// items in chunks of kLW * 64 (shared prefixes recomputed from the keys, record offsets from a
+// scan), then marker / hash-index bytes / trailer, the payload xxh3_128 and the header, and the
+// copy-out.  With more than one wave the hash is xxh3_128_workgroup's (psum and contrib are
+// theirs alone); one wave per 20-96 KiB block ran the 64 KiB classes at 0.18 TB/s.  Every thread
+// of the workgroup calls it; the overflow return is uniform.
 template <uint32_t kLW, int kOW>
-__device__ __forceinline__ void write_block_lds_mw(const EncodeParams& P, uint32_t b, uint8_t* smem, uint32_t* psum,
+__device__ __forceinline__ void write_listed_block(const EncodeParams& P, uint32_t b, uint8_t* smem, uint32_t* psum,
                                                    uint64_t* contrib) {
   constexpr uint32_t kT = kLW * kWave;
-  const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1);
+  const uint32_t tid = threadIdx.x;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(tid / kWave);
-  const uint32_t s = P.starts[b], e = P.starts[b + 1];
-  const uint64_t dst_off = P.block_off[b], dst_end = P.block_off[b + 1];
   const BlockPlan pl = P.plans[b];
-  const uint32_t step = pl.step_flags & 0xFF;
-  if (dst_end > P.out_cap) {
+  const ListedGeom g = listed_geom(P, b, pl);
+  if (g.overflow) {
     if (tid == 0) P.status[b] = ST_OVERFLOW;
     return;
   }
-  const uint32_t n = e - s;
-  const uint32_t ri = is_index(P) ? 1 : P.ri;
-  const uint32_t total = (uint32_t)(dst_end - dst_off);
-  const uint64_t dabs = (uint64_t)(uintptr_t)P.out + dst_off;
-  const uint32_t pad = (uint32_t)(dabs & 15);
   uint8_t* img = smem;
-  uint32_t* hlo = reinterpret_cast<uint32_t*>(smem + ((pad + total + 15) & ~15u) + 32);
+  uint32_t* hlo = reinterpret_cast<uint32_t*>(smem + ((g.pad + g.total + 15) & ~15u) + 32);
   uint32_t* hhi = hlo + ((pl.hash_w + 3) & ~3u);
   for (uint32_t k = tid; k < pl.hash_w; k += kT) {
     hlo[k] = 0xFFFFFFFFu;
     hhi[k] = 0;
   }
-  __syncthreads();
-  const uint32_t p0 = pad + kHdrLen;
-  const uint32_t bin_off = pl.recs + 1;
+  writer_sync<kLW>();
+  const uint32_t s = g.s, n = g.n, ri = g.ri, step = g.step, p0 = g.p0, bin_off = g.bin_off;
   uint32_t carry = 0;
   for (uint32_t c = 0; c < n; c += kT) {
     const uint32_t j = c + tid;
@@ -343,16 +360,8 @@ __device__ __forceinline__ void write_block_lds_mw(const EncodeParams& P, uint32
       m = load_item_lcp<kOW>(P, s, j, ri, bad);
       rec = (uint32_t)item_record_len(P, m, head);
     }
-    const uint32_t incl = wave_incl_scan_u32(rec);
-    if (lane == kWave - 1) psum[wave] = incl;
-    __syncthreads();
-    uint32_t wbase = 0, tot = 0;
-    for (uint32_t w = 0; w < kLW; ++w) {
-      const uint32_t v = psum[w];
-      wbase += w < wave ? v : 0u;
-      tot += v;
-    }
-    const uint32_t roff = carry + wbase + incl - rec;
+    uint32_t tot;
+    const uint32_t roff = carry + wg_excl_scan<kLW>(rec, psum, &tot);
     if (j < n) {
       rc.issue(P, m, head, p0 + roff);
       rc.store(P, m, head, img);
@@ -364,60 +373,38 @@ __device__ __forceinline__ void write_block_lds_mw(const EncodeParams& P, uint32
       }
     }
     carry += tot;
-    __syncthreads();  // (psum is rewritten by the next chunk; the votes are complete)
+    if constexpr (kLW > 1) __syncthreads();  // (psum is rewritten by the next chunk; the votes are complete)
   }
-  const uint32_t plen = total - kHdrLen;
-  const uint32_t hash_off = pl.hash_w ? bin_off + pl.bin_len * step : 0;
+  if constexpr (kLW == 1) wave_lds_sync();  // (one wave: no barrier per chunk)
   if (tid == 0) img[p0 + pl.recs] = kTrailerMarker;
-  for (uint32_t k = tid; k < pl.hash_w; k += kT) img[p0 + hash_off + k] = (uint8_t)bucket_byte(hlo[k], hhi[k]);
-  if (wave == 0) write_trailer_bytes(img, p0 + plen - kTrailerLen, ri, step, pl.bin_len, bin_off, pl.hash_w, hash_off, n);
-  __syncthreads();
-  uint64_t lo = 0, hi = 0;
-  if (plen > 240) {
-    const int q = lane & 3;
-    uint64_t a0, a1;
-    xxh3_acc_init(q, a0, a1);
-    const uint64_t scr0 = kLongSecret.acc[16 + 2 * q], scr1 = kLongSecret.acc[16 + 2 * q + 1];
-    const uint32_t nbk = (plen - 1) / 1024;
-    for (uint32_t n0 = 0; n0 < nbk; n0 += 64) {
-      const uint32_t n1 = min(nbk, n0 + 64);
-      xxh3_kib_contribs(img, p0 + 1024 * n0, (n1 - n0) * 1024 + 1, &kLongSecret, contrib, wave, kLW);
-      __syncthreads();
-      if (wave == 0) xxh3_quad_chain<1>(contrib + 2 * q, n1 - n0, scr0, scr1, a0, a1);
-      __syncthreads();
-    }
-    if (wave == 0) xxh3_wave_tail_merge(img, p0, plen, &kLongSecret, a0, a1, lo, hi);
-  } else if (wave == 0) {
-    xxh3_128_wave(img, p0, plen, &kLongSecret, lo, hi);
+  for (uint32_t k = tid; k < pl.hash_w; k += kT) img[p0 + g.hash_off + k] = (uint8_t)bucket_byte(hlo[k], hhi[k]);
+  if (wave == 0)
+    write_trailer_bytes(img, p0 + g.plen - kTrailerLen, ri, step, pl.bin_len, bin_off, pl.hash_w, g.hash_off, n);
+  writer_sync<kLW>();
+  if (!(kDiagBuild && (P.diag & kDiagNoHash))) {
+    uint64_t lo, hi;
+    if constexpr (kLW == 1) xxh3_128_wave(img, p0, g.plen, &kLongSecret, lo, hi);
+    else xxh3_128_workgroup<true>(img, p0, g.plen, contrib, wave, kLW, lo, hi);
+    if (wave == 0) write_header_bytes(img, g.pad, P.type, lo, hi, g.plen);
   }
-  if (wave == 0) write_header_bytes(img, pad, P.type, lo, hi, plen);
-  __syncthreads();
-  uint8_t* gdst = reinterpret_cast<uint8_t*>(dabs & ~15ULL);
-  const uint32_t chunks = (pad + total + 15) >> 4;
-  for (uint32_t c = tid; c < chunks; c += kT) {
-    const uint32_t clo = c * 16, chi = clo + 16;
-    if (clo >= pad && chi <= pad + total) {
-      copy_store16(reinterpret_cast<u32x4*>(gdst) + c, reinterpret_cast<const u32x4*>(img)[c]);
-    } else {
-      for (uint32_t k = max(clo, pad); k < min(chi, pad + total); ++k) gdst[k] = img[k];
-    }
-  }
+  writer_sync<kLW>();
+  if (!(kDiagBuild && (P.diag & kDiagNoCopyOut))) copy_out_image<kT>(img, g.gdst, g.pad, g.total);
   if (tid == 0) P.status[b] = ST_OK;
-  __syncthreads();  // (the next block reuses the image)
+  if constexpr (kLW > 1) __syncthreads();  // (the next block reuses the image)
 }
 
-// Listed medium / big blocks: one wave per workgroup, grid-stride over the list.
+// Listed medium blocks: one wave per workgroup, grid-stride over the list.
 template <int kOW>
 __global__ __launch_bounds__(kWave) void encode_write_list_kernel(EncodeParams P, uint32_t plan_flag) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const uint32_t count = P.list_count[0];
   for (uint32_t li = blockIdx.x; li < count; li += gridDim.x) {
     const uint32_t b = P.lists[li];
-    if ((P.plans[b].step_flags >> 8) == plan_flag) write_block_lds<kOW>(P, b, smem);
+    if ((P.plans[b].step_flags >> 8) == plan_flag) write_listed_block<1, kOW>(P, b, smem, nullptr, nullptr);
   }
 }
 
-// Listed medium / big blocks, kLW waves per block (write_block_lds_mw).
+// Listed big blocks: kLW waves per block.
 template <uint32_t kLW, int kOW>
 __global__ __launch_bounds__(kLW * kWave) void encode_write_list_mw_kernel(EncodeParams P, uint32_t plan_flag) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -426,7 +413,7 @@ __global__ __launch_bounds__(kLW * kWave) void encode_write_list_mw_kernel(Encod
   const uint32_t count = P.list_count[0];
   for (uint32_t li = blockIdx.x; li < count; li += gridDim.x) {
     const uint32_t b = P.lists[li];
-    if ((P.plans[b].step_flags >> 8) == plan_flag) write_block_lds_mw<kLW, kOW>(P, b, smem, psum, contrib);
+    if ((P.plans[b].step_flags >> 8) == plan_flag) write_listed_block<kLW, kOW>(P, b, smem, psum, contrib);
   }
 }
 
@@ -455,21 +442,13 @@ __global__ __launch_bounds__(kE3Threads) void encode_large_kernel(EncodeParams P
     const uint32_t b = P.lists[li];
     const BlockPlan pl = P.plans[b];
     if ((pl.step_flags >> 8) != kPlanHuge) continue;
-    const uint32_t step = pl.step_flags & 0xFF;
-    const uint64_t dst_off = P.block_off[b], dst_end = P.block_off[b + 1];
-    if (dst_end > P.out_cap) {
+    const ListedGeom g = listed_geom(P, b, pl);
+    if (g.overflow) {
       if (tid == 0) P.status[b] = ST_OVERFLOW;
       continue;
     }
-    const uint32_t s = P.starts[b], e = P.starts[b + 1], n = e - s;
-    const uint32_t ri = is_index(P) ? 1 : P.ri;
-    const uint32_t total = (uint32_t)(dst_end - dst_off);
-    const uint32_t plen = total - kHdrLen;
-    const uint64_t dabs = (uint64_t)(uintptr_t)P.out + dst_off;
-    uint8_t* img = reinterpret_cast<uint8_t*>(dabs & ~15ULL);
-    const uint32_t pad = (uint32_t)(dabs & 15);
-    const uint32_t p0 = pad + kHdrLen;
-    const uint32_t bin_off = pl.recs + 1;
+    const uint32_t s = g.s, n = g.n, ri = g.ri, step = g.step, p0 = g.p0, bin_off = g.bin_off;
+    uint8_t* img = g.gdst;
     const bool scan = n <= kGItems;  // (uniform) else erec holds each record's offset
     const uint32_t pf = P.hb_sh ? P.pfirst[b] : 0u;  // (after E1p erec holds huge blocks' record prefixes)
     for (uint32_t j = tid; j < (scan ? kE3Threads : n); j += kE3Threads) {
@@ -482,13 +461,8 @@ __global__ __launch_bounds__(kE3Threads) void encode_large_kernel(EncodeParams P
         if (!scan) roff = P.erec[s + j] - pf;  // (after E1p: the record prefix, see encode_e1p_offsets_kernel)
       }
       if (scan) {  // n <= kGItems <= kE3Threads: one pass
-        const uint32_t rec = j < n ? (uint32_t)item_record_len(P, m, head) : 0u;
-        const uint32_t incl = wave_incl_scan_u32(rec);
-        if (lane == kWave - 1) psum[wave] = incl;
-        __syncthreads();
-        uint32_t base = 0;
-        for (uint32_t w = 0; w < wave; ++w) base += psum[w];
-        roff = base + incl - rec;
+        uint32_t tot;
+        roff = wg_excl_scan<kE3Waves>(j < n ? (uint32_t)item_record_len(P, m, head) : 0u, psum, &tot);
       }
       if (j < n) {
         RecordCopy rc;
@@ -497,53 +471,17 @@ __global__ __launch_bounds__(kE3Threads) void encode_large_kernel(EncodeParams P
         if (head) store_le(img, p0 + bin_off + (j / ri) * step, roff, step);
       }
     }
-    const uint32_t hash_off = pl.hash_w ? bin_off + pl.bin_len * step : 0;
-    for (uint32_t base = 0; base < pl.hash_w; base += kE3HashChunk) {
-      const uint32_t lim = min(kE3HashChunk, pl.hash_w - base);
-      for (uint32_t k = tid; k < lim; k += kE3Threads) {
-        hlo[k] = 0xFFFFFFFFu;
-        hhi[k] = 0;
-      }
-      __syncthreads();
-      for (uint32_t j = tid; j < n; j += kE3Threads) {
-        const uint64_t i = (uint64_t)s + j;
-        const uint64_t ko = koff<kOW>(P, i);
-        const uint32_t bk = key_bucket(P, ko, (uint32_t)(koff<kOW>(P, i + 1) - ko), pl.hash_w);
-        if (bk >= base && bk < base + lim) {
-          atomicMin(&hlo[bk - base], j / ri);
-          atomicMax(&hhi[bk - base], j / ri);
-        }
-      }
-      __syncthreads();
-      for (uint32_t k = tid; k < lim; k += kE3Threads) img[p0 + hash_off + base + k] = (uint8_t)bucket_byte(hlo[k], hhi[k]);
-      __syncthreads();
-    }
+    hash_index_passes<kE3Threads, kOW>(P, s, n, ri, pl.hash_w, img, p0, g.hash_off, hlo, hhi);
     if (wave == 0) {
       if (lane == 0) img[p0 + pl.recs] = kTrailerMarker;
-      write_trailer_bytes(img, p0 + plen - kTrailerLen, ri, step, pl.bin_len, bin_off, pl.hash_w, hash_off, n);
+      write_trailer_bytes(img, p0 + g.plen - kTrailerLen, ri, step, pl.bin_len, bin_off, pl.hash_w, g.hash_off, n);
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // the block's bytes, for this workgroup's re-reads below
     __syncthreads();
-    uint64_t lo = 0, hi = 0;
-    if (plen > 240) {
-      const int q = lane & 3;
-      uint64_t a0, a1;
-      xxh3_acc_init(q, a0, a1);
-      const uint64_t scr0 = kLongSecret.acc[16 + 2 * q], scr1 = kLongSecret.acc[16 + 2 * q + 1];
-      const uint32_t nbk = (plen - 1) / 1024;
-      for (uint32_t n0 = 0; n0 < nbk; n0 += 64) {
-        const uint32_t n1 = min(nbk, n0 + 64);
-        xxh3_kib_contribs<false>(img, p0 + 1024 * n0, (n1 - n0) * 1024 + 1, &kLongSecret, contrib, wave, kE3Waves);
-        __syncthreads();
-        if (wave == 0) xxh3_quad_chain<1>(contrib + 2 * q, n1 - n0, scr0, scr1, a0, a1);
-        __syncthreads();
-      }
-      if (wave == 0) xxh3_wave_tail_merge(img, p0, plen, &kLongSecret, a0, a1, lo, hi);
-    } else if (wave == 0) {
-      xxh3_128_wave(img, p0, plen, &kLongSecret, lo, hi);
-    }
+    uint64_t lo, hi;
+    xxh3_128_workgroup<false>(img, p0, g.plen, contrib, wave, kE3Waves, lo, hi);
     if (wave == 0) {
-      write_header_bytes(img, pad, P.type, lo, hi, plen);
+      write_header_bytes(img, g.pad, P.type, lo, hi, g.plen);
       if (lane == 0) P.status[b] = ST_OK;
     }
     __syncthreads();
@@ -570,6 +508,7 @@ __global__ __launch_bounds__(kE3Threads) void encode_large_kernel(EncodeParams P
 //            the header and the status
 constexpr uint32_t kEHugeItems = 1024;  // items per record unit, at most (four per thread)
 constexpr uint32_t kEHugeImg = 2 * 4 * kE3HashChunk;  // LDS image of a record unit (the tail unit's vote arrays)
+constexpr uint32_t kEHugeWaves = 4, kEHugeThreads = kEHugeWaves * kWave;  // encode_huge_records_kernel's workgroup
 constexpr uint32_t kEHugeWgsPerCU = 4;  // encode_huge_records_kernel's residency (4 waves per SIMD, 32 KB of LDS)
 
 __device__ __forceinline__ uint32_t last_le_u64(const uint64_t* a, uint32_t n, uint64_t v) {
@@ -656,16 +595,16 @@ __global__ __launch_bounds__(1024) void encode_huge_plan_kernel(EncodeParams P) 
 
 // Record units (u < nru of a block) and the tail unit (u == nru).
 template <int kOW>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void encode_huge_records_kernel(EncodeParams P) {
+__global__ __launch_bounds__(kEHugeThreads) __attribute__((amdgpu_waves_per_eu(4))) void encode_huge_records_kernel(EncodeParams P) {
   __shared__ __attribute__((aligned(16))) uint32_t lbuf[2 * kE3HashChunk];  // record image | vote arrays
   uint32_t* hlo = lbuf;
   uint32_t* hhi = lbuf + kE3HashChunk;
-  __shared__ uint32_t psum[4];
+  __shared__ uint32_t psum[kEHugeWaves];
   const EncHugeLayout L = enc_huge_layout(P);
   const uint32_t n3 = L.hdr->n3;
   if (!n3) return;
   const uint64_t units = L.hdr->total_units;
-  const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
+  const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1), wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   // a run of consecutive units per workgroup: one block search per run
   const uint64_t per = (units + gridDim.x - 1) / gridDim.x;
   const uint64_t u_begin = (uint64_t)blockIdx.x * per, u_end = min(units, u_begin + per);
@@ -689,28 +628,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void e
     if (!h.accepted) continue;  // (uniform; rejected blocks own no units)
     const uint32_t k = (uint32_t)(u - gload(L.upre, i));
     const BlockPlan pl = gload_pod(P.plans, h.b);
-    const uint32_t step = pl.step_flags & 0xFF;
     const uint32_t ri = is_index(P) ? 1 : P.ri;
-    const uint32_t plen = h.total - kHdrLen;
-    const uint64_t dabs = (uint64_t)(uintptr_t)P.out + h.dst_off;
-    uint8_t* img = reinterpret_cast<uint8_t*>(dabs & ~15ULL);
-    const uint32_t p0 = (uint32_t)(dabs & 15) + kHdrLen;
-    const uint32_t bin_off = pl.recs + 1;
     REC_PHASE(0);
     if (k < h.nru) {
+      // (the geometry is built in each arm, not once above them: built there, this kernel, which is
+      // held to 128 VGPRs, spilled 32 bytes per lane more)
+      const ListedGeom g = listed_geom(P, h, pl);
+      const uint32_t step = g.step, p0 = g.p0, bin_off = g.bin_off;
+      uint8_t* img = g.gdst;
       if (h.n <= kGItems) {  // one pass: record offsets from a workgroup scan
         const uint32_t j = tid;
         const bool head = j % ri == 0;
         ItemMeta m;
         bool bad = false;
         if (j < h.n) m = load_item_lcp<kOW>(P, h.s, j, ri, bad);
+        uint32_t tot;
         const uint32_t rec = j < h.n ? (uint32_t)item_record_len(P, m, head) : 0u;
-        const uint32_t incl = wave_incl_scan_u32(rec);
-        if (lane == kWave - 1) psum[wave] = incl;
-        __syncthreads();
-        uint32_t base = 0;
-        for (uint32_t w = 0; w < wave; ++w) base += psum[w];
-        const uint32_t roff = base + incl - rec;
+        const uint32_t roff = wg_excl_scan<kEHugeWaves>(rec, psum, &tot);
         if (j < h.n) {
           RecordCopy rc;
           rc.issue(P, m, head, p0 + roff);
@@ -754,7 +688,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void e
             if (g1 > g0) {
               const uint64_t kg = gload(L.kpre, i) + g0;
               xxh3_kib_contribs(reinterpret_cast<const uint8_t*>(lbuf), p0 + 1024 * g0 - a0, (g1 - g0) * 1024 + 1,
-                                &kLongSecret, L.contrib + 8 * kg, wave, 4);  // (lbuf-relative: ds_read, not flat)
+                                &kLongSecret, L.contrib + 8 * kg, wave, kEHugeWaves);  // (lbuf-relative: ds_read, not flat)
               for (uint32_t g = tid; g < g1 - g0; g += 256) L.kdone[kg + g] = 1;
             }
           }
@@ -780,30 +714,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void e
       continue;
     }
     // tail unit: hash-index votes (LDS passes), marker, trailer
-    const uint32_t hash_off = pl.hash_w ? bin_off + pl.bin_len * step : 0;
-    for (uint32_t base = 0; base < pl.hash_w; base += kE3HashChunk) {
-      const uint32_t lim = min(kE3HashChunk, pl.hash_w - base);
-      for (uint32_t q = tid; q < lim; q += 256) {
-        hlo[q] = 0xFFFFFFFFu;
-        hhi[q] = 0;
-      }
-      __syncthreads();
-      for (uint32_t j = tid; j < h.n; j += 256) {
-        const uint64_t it = (uint64_t)h.s + j;
-        const uint64_t ko = koff<kOW>(P, it);
-        const uint32_t bk = key_bucket(P, ko, (uint32_t)(koff<kOW>(P, it + 1) - ko), pl.hash_w);
-        if (bk >= base && bk < base + lim) {
-          atomicMin(&hlo[bk - base], j / ri);
-          atomicMax(&hhi[bk - base], j / ri);
-        }
-      }
-      __syncthreads();
-      for (uint32_t q = tid; q < lim; q += 256) img[p0 + hash_off + base + q] = (uint8_t)bucket_byte(hlo[q], hhi[q]);
-      __syncthreads();
-    }
+    const ListedGeom g = listed_geom(P, h, pl);
+    const uint32_t step = g.step, p0 = g.p0, bin_off = g.bin_off;
+    uint8_t* img = g.gdst;
+    hash_index_passes<kEHugeThreads, kOW>(P, h.s, h.n, ri, pl.hash_w, img, p0, g.hash_off, hlo, hhi);
     if (wave == 0) {
       if (lane == 0) img[p0 + pl.recs] = kTrailerMarker;
-      write_trailer_bytes(img, p0 + plen - kTrailerLen, ri, step, pl.bin_len, bin_off, pl.hash_w, hash_off, h.n);
+      write_trailer_bytes(img, p0 + g.plen - kTrailerLen, ri, step, pl.bin_len, bin_off, pl.hash_w, g.hash_off, h.n);
     }
     REC_PHASE(5);
   }
@@ -968,7 +885,8 @@ hipError_t launch_encode_large(const EncodeParams& P, hipStream_t st) {
       // 0.459 -> 0.424 ms against a 2048-workgroup grid)
       int n_cu = 0;
       if ((e = device_cu_count(&n_cu)) != hipSuccess) return e;
-      hipLaunchKernelGGL(encode_huge_records_kernel<kOW>, dim3(kEHugeWgsPerCU * (uint32_t)n_cu), dim3(256), 0, st, P);
+      hipLaunchKernelGGL(encode_huge_records_kernel<kOW>, dim3(kEHugeWgsPerCU * (uint32_t)n_cu), dim3(kEHugeThreads), 0,
+                         st, P);
       hipLaunchKernelGGL(encode_huge_chain_kernel, dim3(min(P.n_blocks, 1024u)), dim3(256), 0, st, P);
     }
     hipLaunchKernelGGL(encode_large_kernel<kOW>, dim3(512), dim3(kE3Threads), 0, st, P);

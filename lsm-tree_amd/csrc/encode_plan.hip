@@ -171,28 +171,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void e
   __syncthreads();
   if (tid >= nb) return;
   const uint32_t b = b0 + tid, s = bst[tid], e = bst[tid + 1];
-  bool bad = !mono || e <= s || badf[tid] || start_past_items(P, b + 1);
-  const uint32_t n = bad ? 0 : e - s;
-  const uint64_t recs = bad ? 0 : bend[tid] - bfirst[tid], last_head = bad ? 0 : lhead[tid] - bfirst[tid];
-  const uint32_t bin_len = n ? (n + ri - 1) / ri : 0;
-  const uint32_t step = last_head <= 0xFFFF ? 2 : 4;
-  const uint32_t buckets = kIndex ? 0 : bucket_count(n, P.ratio);
-  const uint32_t hash_w = (buckets > 0 && bin_len <= kHashMaxPointers) ? buckets : 0;
-  const uint64_t total = kHdrLen + recs + 1 + (uint64_t)bin_len * step + hash_w + kTrailerLen;
-  if (recs > 0xFFFFFFF0ULL || total > 0xFFFFFF00ULL) bad = true;
+  const bool bad = !mono || e <= s || badf[tid] || start_past_items(P, b + 1);
   const uint64_t ks = koff(P, s), ke = koff(P, e);
   const uint64_t vs = kIndex ? 0 : voff(P, s), ve = kIndex ? 0 : voff(P, e);
-  uint32_t flags = 0;
-  if (bad) {
-    flags = kPlanBad;
-    P.status[b] = ST_BAD_ARG;
-  } else if (!group_fits(n, ke - ks, ve - vs, total, hash_w)) {
-    const uint64_t need = e2_need(total, hash_w);
-    flags = need <= kImgMedium ? kPlanMedium : need <= kImgBig ? kPlanBig : kPlanHuge;
-  }
-  P.plans[b] = BlockPlan{(uint32_t)recs, bin_len, hash_w, step | (flags << 8)};
-  // bits 40.. count the listed (not group) blocks: the size scan numbers them
-  P.sizes[b] = (bad ? 0 : total) | ((flags & (kPlanMedium | kPlanBig | kPlanHuge)) ? kListedOne : 0);
+  BlockPlan pl;
+  P.sizes[b] =
+      plan_block<kIndex>(P, b, s, e, bad, bend[tid] - bfirst[tid], lhead[tid] - bfirst[tid], ks, ke, vs, ve, pl);
   P.kspan[b] = ks;
   P.vspan[b] = vs;
   if (b + 1 == P.n_blocks) {
@@ -220,8 +204,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void e
 //            or the parts at a wave's two ends)
 //   scan     the device scan over every item's record length, in place (low
 //            32 bits: a block's offsets are differences of two prefixes)
-//   blocks   wave per block: its total from the wave parts, the plan as
-//            encode_plan_kernel's epilogue
+//   blocks   wave per block: its total from the wave parts, then plan_block
 //   offsets  thread per item: erec = prefix - its block's first prefix (the
 //            packed word for blocks of <= kGItems items); huge blocks keep the
 //            prefix (their writers subtract pfirst)
@@ -409,7 +392,7 @@ __device__ __forceinline__ uint32_t e1p_prefix(const EncodeParams& P, uint32_t i
 }
 
 // Wave per block: its record total from the lengths kernel's per-wave parts,
-// then the plan (encode_plan_kernel's epilogue) on lane 0.
+// then the plan (plan_block) on lane 0.
 __global__ __launch_bounds__(256) void encode_e1p_blocks_kernel(EncodeParams P) {
   const uint32_t lane = threadIdx.x & 63;
   const uint64_t bq = ((uint64_t)blockIdx.x * 256 + threadIdx.x) / 64;
@@ -430,30 +413,15 @@ __global__ __launch_bounds__(256) void encode_e1p_blocks_kernel(EncodeParams P) 
     }
   }
   if (lane) return;
-  bool bad = P.e1p_flag[0] || e <= s || (acc & kE1pBad) || start_past_items(P, b + 1);
-  const uint32_t n = bad ? 0 : e - s;
-  const uint64_t recs = bad ? 0 : acc & ~kE1pBad;
+  const bool bad = P.e1p_flag[0] || e <= s || (acc & kE1pBad) || start_past_items(P, b + 1);
   const uint32_t p_s = bad ? 0 : e1p_prefix(P, s);
   P.pfirst[b] = p_s;
-  const uint32_t bin_len = n ? (n + ri - 1) / ri : 0;
-  const uint64_t last_head = n ? (uint32_t)(e1p_prefix(P, s + (bin_len - 1) * ri) - p_s) : 0;
-  const uint32_t step = last_head <= 0xFFFF ? 2 : 4;
-  const uint32_t buckets = bucket_count(n, P.ratio);
-  const uint32_t hash_w = (buckets > 0 && bin_len <= kHashMaxPointers) ? buckets : 0;
-  const uint64_t total = kHdrLen + recs + 1 + (uint64_t)bin_len * step + hash_w + kTrailerLen;
-  if (recs > 0xFFFFFFF0ULL || total > 0xFFFFFF00ULL) bad = true;
+  // (the last restart head: item ((n - 1) / ri) * ri of the block)
+  const uint64_t last_head = bad ? 0 : (uint32_t)(e1p_prefix(P, s + (e - s - 1) / ri * ri) - p_s);
   const uint64_t ks = koff(P, s), ke = koff(P, e);
   const uint64_t vs = voff(P, s), ve = voff(P, e);
-  uint32_t flags = 0;
-  if (bad) {
-    flags = kPlanBad;
-    P.status[b] = ST_BAD_ARG;
-  } else if (!group_fits(n, ke - ks, ve - vs, total, hash_w)) {
-    const uint64_t need = e2_need(total, hash_w);
-    flags = need <= kImgMedium ? kPlanMedium : need <= kImgBig ? kPlanBig : kPlanHuge;
-  }
-  P.plans[b] = BlockPlan{(uint32_t)recs, bin_len, hash_w, step | (flags << 8)};
-  P.sizes[b] = (bad ? 0 : total) | ((flags & (kPlanMedium | kPlanBig | kPlanHuge)) ? kListedOne : 0);
+  BlockPlan pl;
+  P.sizes[b] = plan_block<false>(P, b, s, e, bad, acc & ~kE1pBad, last_head, ks, ke, vs, ve, pl);
   P.kspan[b] = ks;
   P.vspan[b] = vs;
   if (b + 1 == P.n_blocks) {

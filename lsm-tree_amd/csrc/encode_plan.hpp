@@ -12,6 +12,38 @@ __device__ __forceinline__ uint64_t e2_need(uint64_t total, uint32_t hash_w) {
   return ((15 + total + 15) & ~15ULL) + 32 + 8ULL * ((hash_w + 3) & ~3u);
 }
 
+// The plan of block b = items [s, e), from what its plan kernel found: `bad` (a caller error in the
+// block's range or items), the bytes of its records, its last restart head's offset, and the key /
+// value offsets at s and e.  Sizes the binary and the hash index, checks the limits, picks the class
+// (group_fits, else by e2_need), stores P.plans[b] (and ST_BAD_ARG) and returns the block's word for
+// the size scan: its bytes, 0 for a bad block, plus kListedOne (bits 40..: the scan numbers the
+// listed blocks) if no group takes it.
+template <bool kIndex>
+__device__ __forceinline__ uint64_t plan_block(const EncodeParams& P, uint32_t b, uint32_t s, uint32_t e, bool bad,
+                                               uint64_t recs, uint64_t last_head, uint64_t ks, uint64_t ke,
+                                               uint64_t vs, uint64_t ve, BlockPlan& pl) {
+  const uint32_t ri = kIndex ? 1 : P.ri;
+  const uint32_t n = bad ? 0 : e - s;
+  if (bad) recs = last_head = 0;
+  const uint32_t bin_len = n ? (n + ri - 1) / ri : 0;
+  const uint32_t step = last_head <= 0xFFFF ? 2 : 4;
+  const uint32_t buckets = kIndex ? 0 : bucket_count(n, P.ratio);
+  const uint32_t hash_w = (buckets > 0 && bin_len <= kHashMaxPointers) ? buckets : 0;
+  const uint64_t total = kHdrLen + recs + 1 + (uint64_t)bin_len * step + hash_w + kTrailerLen;
+  if (recs > 0xFFFFFFF0ULL || total > 0xFFFFFF00ULL) bad = true;
+  uint32_t flags = 0;
+  if (bad) {
+    flags = kPlanBad;
+    P.status[b] = ST_BAD_ARG;
+  } else if (!group_fits(n, ke - ks, ve - vs, total, hash_w)) {
+    const uint64_t need = e2_need(total, hash_w);
+    flags = need <= kImgMedium ? kPlanMedium : need <= kImgBig ? kPlanBig : kPlanHuge;
+  }
+  pl = BlockPlan{(uint32_t)recs, bin_len, hash_w, step | (flags << 8)};
+  P.plans[b] = pl;
+  return (bad ? 0 : total) | ((flags & (kPlanMedium | kPlanBig | kPlanHuge)) ? kListedOne : 0);
+}
+
 // 16 bytes at p (global, any alignment): one unaligned 16-B load (the arenas are
 // padded).  Two aligned loads and a funnel shift issued twice the loads and ~10 VALU
 // more per window, and held 20 more VGPRs in the plan kernel (113 -> 93, u32 offsets):
@@ -288,28 +320,12 @@ __device__ __forceinline__ void plan_wave_run(const EncodeParams& P, uint32_t b0
   __syncthreads();
   if (tid >= nb) return;
   const uint32_t b = b0 + tid, s = bst[tid], e = bst[tid + 1];
-  bool bad = !mono || e <= s || badf[tid] || start_past_items(P, b + 1);
-  const uint32_t n = bad ? 0 : e - s;
-  const uint64_t recs = bad ? 0 : bend[tid] - bfirst[tid], last_head = bad ? 0 : lhead[tid] - bfirst[tid];
-  const uint32_t bin_len = n ? (n + ri - 1) / ri : 0;
-  const uint32_t step = last_head <= 0xFFFF ? 2 : 4;
-  const uint32_t buckets = bucket_count(n, P.ratio);
-  const uint32_t hash_w = (buckets > 0 && bin_len <= kHashMaxPointers) ? buckets : 0;
-  const uint64_t total = kHdrLen + recs + 1 + (uint64_t)bin_len * step + hash_w + kTrailerLen;
-  if (recs > 0xFFFFFFF0ULL || total > 0xFFFFFF00ULL) bad = true;
+  const bool bad = !mono || e <= s || badf[tid] || start_past_items(P, b + 1);
   const uint64_t ks = koff<kOW>(P, s), ke = koff<kOW>(P, e);
   const uint64_t vs = voff<kOW>(P, s), ve = voff<kOW>(P, e);
-  uint32_t flags = 0;
-  if (bad) {
-    flags = kPlanBad;
-    P.status[b] = ST_BAD_ARG;
-  } else if (!group_fits(n, ke - ks, ve - vs, total, hash_w)) {
-    const uint64_t need = e2_need(total, hash_w);
-    flags = need <= kImgMedium ? kPlanMedium : need <= kImgBig ? kPlanBig : kPlanHuge;
-  }
-  const BlockPlan pl{(uint32_t)recs, bin_len, hash_w, step | (flags << 8)};
-  const uint64_t size = (bad ? 0 : total) | ((flags & (kPlanMedium | kPlanBig | kPlanHuge)) ? kListedOne : 0);
-  P.plans[b] = pl;
+  BlockPlan pl;
+  const uint64_t size =
+      plan_block<false>(P, b, s, e, bad, bend[tid] - bfirst[tid], lhead[tid] - bfirst[tid], ks, ke, vs, ve, pl);
   if (kFused) {
     fplan[tid] = pl;
     fsize[tid] = size;

@@ -925,6 +925,35 @@ __device__ __forceinline__ void xxh3_128_wave(const uint8_t* base, uint32_t pos,
   }
 }
 
+// XXH3-128 of img[p0 .. p0 + plen) by the n_waves waves of a workgroup.  Every thread calls it
+// with the same arguments (it holds workgroup barriers), the bytes visible to the workgroup.  Per
+// 64 KiB every wave reduces KiB blocks into `contrib` (LDS, 8 x 64 words: xxh3_kib_contribs), then
+// wave 0 carries the scramble chain over them in order; it ends with the tail and the merge, or
+// hashes an input of <= 240 bytes by itself.  lo / hi are valid on wave 0.  kFromLds: img is an LDS
+// image, else HBM.
+template <bool kFromLds>
+__device__ __forceinline__ void xxh3_128_workgroup(const uint8_t* img, uint32_t p0, uint32_t plen, uint64_t* contrib,
+                                                   uint32_t wave, uint32_t n_waves, uint64_t& lo, uint64_t& hi) {
+  lo = hi = 0;
+  if (plen > 240) {
+    const int q = threadIdx.x & 3;
+    uint64_t a0, a1;
+    xxh3_acc_init(q, a0, a1);
+    const uint64_t scr0 = kLongSecret.acc[16 + 2 * q], scr1 = kLongSecret.acc[16 + 2 * q + 1];
+    const uint32_t nbk = (plen - 1) / 1024;
+    for (uint32_t n0 = 0; n0 < nbk; n0 += 64) {
+      const uint32_t n1 = min(nbk, n0 + 64);
+      xxh3_kib_contribs<kFromLds>(img, p0 + 1024 * n0, (n1 - n0) * 1024 + 1, &kLongSecret, contrib, wave, n_waves);
+      __syncthreads();
+      if (wave == 0) xxh3_quad_chain<1>(contrib + 2 * q, n1 - n0, scr0, scr1, a0, a1);
+      __syncthreads();
+    }
+    if (wave == 0) xxh3_wave_tail_merge(img, p0, plen, &kLongSecret, a0, a1, lo, hi);
+  } else if (wave == 0) {
+    xxh3_128_wave(img, p0, plen, &kLongSecret, lo, hi);
+  }
+}
+
 // Per-lane XXH3-64 for inputs > 240 B (hash-index keys longer than 240 B;
 // rare).  Scalar restatement of hashLong + mergeAccs on one lane.
 template <class R64>

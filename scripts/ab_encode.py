@@ -5,7 +5,9 @@ usage: scripts/ab_encode.py LIB1 LIB2 ... [--rounds 3]
 Each round runs every library in its own child process (interleaved, rule 24 of
 the HIP guide); a child times lsm_encode_blocks on configs[1] (1 M x 4 KiB) and
 configs[3] (256 K x 16 KiB prefix keys) and prints the xxh3_128 of the encoded
-bytes, so variants can be compared for identical output.
+bytes, so variants can be compared for identical output.  --which takes other
+shapes (see `shapes`); NAME_32 is a shape through lsm_encode_blocks32, NAME_np
+the shape without the workspace pool.
 """
 import json
 import os
@@ -38,26 +40,28 @@ def child(reps, which):
               "l4m": dict(n_blocks=60, items_per_block=52429, seed=0x5EED0007)}
     for name in which.split(","):
         off32 = name.endswith("_32")  # the same shape through lsm_encode_blocks32 (u32 offsets)
-        base = name[:-3] if off32 else name
+        nopool = name.endswith("_np")  # the same shape without the workspace pool (huge blocks: one workgroup each)
+        base = name[:-3] if off32 or nopool else name
         items, starts, n = bench.make_workload(torch, lsmgpu, **shapes[base])
         if off32:
             items = dict(items, key_off=items["key_off"].to(torch.int32), val_off=items["val_off"].to(torch.int32))
         nb = shapes[base]["n_blocks"]
         hr = 1.33 if base == "h1" else 0.0
         enc_ctx = lsmgpu.Encoder()
-        enc = enc_ctx.encode(items, starts, nb, hash_ratio=hr)
+        kw = dict(hash_ratio=hr, pool=False) if nopool else dict(hash_ratio=hr)
+        enc = enc_ctx.encode(items, starts, nb, **kw)
         torch.cuda.synchronize()
         total = int(enc["block_off"][nb].item())
         bad = int((enc["status"][:nb] != 0).sum())
         # untimed warm-up calls: without them the first shape of a child ran ~3-5 % slow
         # (clocks / allocator still settling), which biased cross-shape comparisons
         for _ in range(5):
-            enc_ctx.encode(items, starts, nb, hash_ratio=hr, out=enc)
+            enc_ctx.encode(items, starts, nb, out=enc, **kw)
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(reps):
-            enc_ctx.encode(items, starts, nb, hash_ratio=hr, out=enc)
+            enc_ctx.encode(items, starts, nb, out=enc, **kw)
         e1.record()
         torch.cuda.synchronize()
         ms = e0.elapsed_time(e1) / reps
