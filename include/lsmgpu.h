@@ -51,6 +51,11 @@
  *                         block, BlockIndex::forward_reader over FullBlockIndex / TwoLevelBlockIndex,
  *                         index_block::Iter::seek index_block/iter.rs:25-34, load_data_block +
  *                         DataBlock::point_read)
+ *   lsm_table_range    <- Table::range             src/table/mod.rs:391-422, the forward drain of the table
+ *                         Iter src/table/iter.rs:94-293 (index seeks iter.rs:186-221, both data-block seeks
+ *                         per block iter.rs:272-277), index_block::Iter::seek / seek_upper
+ *                         index_block/iter.rs:25-40 over partition_point_2 block/decoder.rs:210-256,
+ *                         TwoLevelBlockIndex's Iter block_index/two_level.rs:78-173
  *   lsm_merge_runs     <- Merger::new / next       src/merge.rs:34-100
  *                         CompactionStream          src/compaction/stream.rs:46-221
  *                         InternalKey Ord           src/key.rs:59-72
@@ -762,6 +767,90 @@ int lsm_table_get(const uint8_t* d_file, uint64_t file_len, const lsm_table_scan
                   const uint64_t* d_key_hash, const uint8_t* d_active, uint32_t n_queries,
                   const lsm_point_result* d_out, uint64_t* d_hit_block_off, uint32_t* d_hit_block_size,
                   uint8_t* d_outcome, int32_t* d_status, void* stream);
+
+/* ---- range bounds in a table (Table::range, src/table/mod.rs:391-422) ----------
+ * Batched Table::range(bounds) on one table file image d_file[0 .. file_len) (same
+ * buffer rules as lsm_table_get): per query, the position of the first and of the last
+ * row that a forward drain (next() only) of the range yields (table Iter,
+ * src/table/iter.rs:94-293).  Both index levels are searched on the device, so the
+ * caller names no block.  table: tli_off, tli_size and two_level as for lsm_scan_table;
+ * global_seqno and block_count are ignored (positions carry no seqno).  Bounds and
+ * d_flags exactly as lsm_seek_blocks: query q's lower bound is
+ * d_lo[d_lo_off[q] .. d_lo_off[q+1]), its upper bound d_hi[d_hi_off[q] .. d_hi_off[q+1])
+ * (arenas 16-byte aligned, readable LSM_INPUT_PADDING bytes past their end; none of the
+ * four pointers may be NULL), d_flags[q] the LSM_SEEK_* bits; a bound whose bit is clear
+ * is unbounded.
+ * Per query:
+ *  1. the index seeks, with seqno u64::MAX (iter.rs:196,208).  An index block (restart
+ *     interval 1, else LSM_PARSE) yields its entries a..=b, none if a > b
+ *     (block/decoder.rs:443-447).  With a lower bound, a = the first entry failing
+ *     end_key < lo || (end_key == lo && seqno >= u64::MAX) (index_block/iter.rs:25-34);
+ *     no such entry ends the index drain; without one a = 0.  With an upper bound,
+ *     b = the first entry with end_key > hi, or the last entry if there is none
+ *     (iter.rs:36-40 over partition_point_2, block/decoder.rs:210-256, which clamps);
+ *     without one b = the last entry.  Full index: the handle list H is the TLI's span.
+ *     Two-level (block_index/two_level.rs:78-173): the TLI's span names the partitions,
+ *     each is loaded and spanned with the same two seeks, H is their spans in order; a
+ *     partition whose lower seek finds nothing ends H, the partitions after it included;
+ *  2. every handle of H is a data block (type Data), seeked with both bounds as
+ *     lsm_seek_blocks does (iter.rs:272-277), the crossing clamp included: [first, end).
+ *     The drain is those ranges in H order.  Versions of one user key straddle blocks (the
+ *     writer cuts by size), so the first and the last block of H may yield nothing.
+ * The first row is `first` of the first block of H with a non-empty range, the last row
+ * `end - 1` of the last such block.  d_outcome[q] = LSM_RANGE_ROWS if there is such a
+ * block, LSM_RANGE_EMPTY if H is non-empty and there is none, LSM_RANGE_NO_BLOCK if H is
+ * empty.  For every outcome but LSM_RANGE_ROWS only d_outcome[q] and d_status[q] are
+ * written.
+ * Reading order (it decides which fault a query reports): the TLI; H forwards until a
+ * block yields a row or H ends (partitions loaded as they are reached); H backwards from
+ * its end until a block yields a row, at the latest down to the first row's block, which
+ * is not loaded twice.  Blocks strictly between the two rows are never read: a fault in
+ * them is not seen.  Walking backwards, a partition whose lower seek finds nothing counts
+ * as empty; on a table whose TLI and partitions agree there is none in the TLI's span.
+ * Outputs (d_out: the address of an lsm_range_result, a host struct of device arrays,
+ * passed as const void*; NULL fields are not written, first_item and last_item are
+ * required): the handles of the two blocks, the items' indices in their
+ * blocks (last_item inclusive), and, with d_data_block_off (n_data_blocks + 1 u64, the
+ * table's data-block offsets as lsm_scan_table and the table writer leave them; may be
+ * NULL), the two blocks' ordinals in it, found by binary search; a handle that is not
+ * exactly [off[i], off[i+1]) gives that query LSM_BAD_ARG and LSM_RANGE_NONE (the array is
+ * not this table's).  The positions are the reference's on any table whose index levels
+ * agree with each other; data blocks may disagree with the index.  On a table as the
+ * writer writes it the drain is exactly the rows from the first to the last position in
+ * file order, so with the d_item_start of a scan the answer is the row window
+ * [item_start[first_block] + first_item, item_start[last_block] + last_item + 1).
+ * d_status[q]: as lsm_table_get (LSM_BAD_MAGIC / LSM_BAD_TYPE / LSM_TRUNCATED from a block
+ * header; LSM_TYPE_MISMATCH: TLI or partition not Index, data block not Data; LSM_PARSE:
+ * trailer or record malformed; LSM_TRUNCATED: a handle shorter than a header or ending
+ * past file_len, or data_length != size - 33; LSM_UNSUPPORTED: a compressed block, i.e. an
+ * LZ4 table).  Payload checksums are verified upstream, as for lsm_table_get.  No byte
+ * outside d_file[0 .. file_len + LSM_INPUT_PADDING) is read, whatever the file holds.
+ * Asynchronous on `stream`: no host synchronisation, no workspace, capturable.
+ * LSM_BAD_ARG (before any device work): a NULL required pointer (d_outcome and d_status
+ * are required), d_file / d_lo / d_hi not 16-byte aligned, two_level > 1, the TLI outside
+ * the file, first_block or last_block requested with d_data_block_off == NULL. */
+typedef struct lsm_range_result {
+    uint64_t* first_block_off;
+    uint32_t* first_block_size;
+    uint32_t* first_item;
+    uint64_t* last_block_off;
+    uint32_t* last_block_size;
+    uint32_t* last_item;   /* inclusive */
+    uint32_t* first_block; /* ordinals in d_data_block_off */
+    uint32_t* last_block;
+} lsm_range_result;
+enum {
+    LSM_RANGE_NONE = 0,     /* d_status[q] != LSM_OK */
+    LSM_RANGE_NO_BLOCK = 1, /* the index seeks name no data block: none was loaded */
+    LSM_RANGE_EMPTY = 2,    /* data blocks were loaded, none yields a row */
+    LSM_RANGE_ROWS = 3
+};
+int lsm_table_range(const uint8_t* d_file, uint64_t file_len, const lsm_table_scan* table,
+                    const uint8_t* d_lo, const uint64_t* d_lo_off, const uint8_t* d_hi, const uint64_t* d_hi_off,
+                    const uint8_t* d_flags, uint32_t n_queries,
+                    const uint64_t* d_data_block_off, uint32_t n_data_blocks,
+                    const void* d_out /* const lsm_range_result* */, uint8_t* d_outcome, int32_t* d_status,
+                    void* stream);
 
 /* ---- merge of sorted runs with compaction GC ----------------------------------
  * CompactionStream::new(Merger::new(runs), gc_seqno_threshold)

@@ -51,7 +51,7 @@ inline hipError_t device_cu_count(int* n_cu) {
 
 // The block handle (off, size) holds a header and lies in a file of file_len
 // bytes: the test of both handle kernels of table_scan.hip and, on the TLI's
-// handle, of the tables' entry points (load_block of table_get.hip spells it out).
+// handle, of the tables' entry points (load_block of table_index.hpp spells it out).
 __host__ __device__ inline bool handle_in_file(uint64_t off, uint32_t size, uint64_t file_len) {
   return size >= LSM_HEADER_LEN && off + size >= off && off + size <= file_len;
 }

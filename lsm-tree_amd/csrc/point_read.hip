@@ -105,57 +105,6 @@ struct SeekParams {
   int32_t* status;
 };
 
-// partition_point over the restart heads: pred = head < needle (or <= with le).
-__device__ __forceinline__ int32_t seek_partition(const uint8_t* base, uint32_t p0, const TrailerInfo& t,
-                                                  const uint8_t* nb, uint32_t np, uint32_t nn, bool le,
-                                                  uint32_t& iv) {
-  uint32_t lo = 0, hi = t.bin_len;
-  while (lo < hi) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    Cursor c;
-    c.init(base, p0, bin_get(base, p0, t, mid), t.rec_end);
-    ItemFields f;
-    if (!parse_data_record(c, true, 0, f)) return ST_PARSE;
-    const int cmp = cmp_span(base, p0 + f.key_off, f.key_len, nb, np, nn);
-    if (le ? cmp <= 0 : cmp < 0) lo = mid + 1;
-    else hi = mid;
-  }
-  iv = lo == 0 ? 0 : lo - 1;
-  return ST_OK;
-}
-
-// Forward scan from restart interval iv: index of the first item that stops
-// it (key >= needle, or key > needle with `past_equal`), item_count if none;
-// eq = that item's key equals the needle.
-__device__ __forceinline__ int32_t seek_scan(const uint8_t* base, uint32_t p0, const TrailerInfo& t, uint32_t iv,
-                                             const uint8_t* nb, uint32_t np, uint32_t nn, bool past_equal,
-                                             uint32_t& at, bool& eq, bool& prev_eq) {
-  Cursor c;
-  c.init(base, p0, bin_get(base, p0, t, iv), t.rec_end);
-  uint32_t head_key = 0;
-  at = t.item_count;
-  eq = prev_eq = false;
-  for (uint32_t i = iv * t.ri; i < t.item_count; ++i) {
-    const bool restart = i % t.ri == 0;
-    ItemFields f;
-    if (!parse_data_record(c, restart, head_key, f)) return ST_PARSE;
-    int cmp;
-    if (restart) {
-      head_key = f.key_off;
-      cmp = cmp_span(base, p0 + f.key_off, f.key_len, nb, np, nn);
-    } else {
-      cmp = cmp_prefixed(base, p0 + head_key, f.prefix_len, p0 + f.key_off, f.key_len, nb, np, nn);
-    }
-    if (cmp > 0 || (cmp == 0 && !past_equal)) {
-      at = i;
-      eq = cmp == 0;
-      return ST_OK;
-    }
-    prev_eq = cmp == 0;
-  }
-  return ST_OK;
-}
-
 __global__ __launch_bounds__(256) void seek_kernel(SeekParams P) {
   const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= P.n) return;
@@ -175,36 +124,7 @@ __global__ __launch_bounds__(256) void seek_kernel(SeekParams P) {
   if (st == ST_OK && h.data_length != len - kHdrLen) st = ST_TRUNCATED;
   if (st == ST_OK && h.type != LSM_BLOCK_DATA && h.type != LSM_BLOCK_META) st = ST_TYPE_MISMATCH;
   if (st == ST_OK) st = read_trailer(base, p0, h.data_length, t);
-  if (st == ST_OK) {
-    first = 0;
-    end = t.item_count;
-    if (fl & LSM_SEEK_LO) {  // Iter::seek (iter.rs:37-76) / seek_exclusive (iter.rs:115-145)
-      const uint64_t o = P.lo_off[q];
-      const uint32_t nn = (uint32_t)min(P.lo_off[q + 1] - o, (uint64_t)0xFFFFFFFFu);
-      const uint8_t* nb = P.lo + (o & ~15ULL);
-      const uint32_t np = (uint32_t)(o & 15);
-      const bool excl = (fl & LSM_SEEK_LO_EXCLUSIVE) != 0;
-      uint32_t iv = 0;
-      bool eq = false, prev_eq = false;
-      st = seek_partition(base, p0, t, nb, np, nn, false, iv);
-      if (st == ST_OK) st = seek_scan(base, p0, t, iv, nb, np, nn, excl, first, eq, prev_eq);
-      if (excl ? first < t.item_count : eq) found |= 1;
-    }
-    if (st == ST_OK && (fl & LSM_SEEK_HI)) {  // Iter::seek_upper (iter.rs:78-113) / seek_upper_exclusive (:147-176)
-      const uint64_t o = P.hi_off[q];
-      const uint32_t nn = (uint32_t)min(P.hi_off[q + 1] - o, (uint64_t)0xFFFFFFFFu);
-      const uint8_t* nb = P.hi + (o & ~15ULL);
-      const uint32_t np = (uint32_t)(o & 15);
-      const bool excl = (fl & LSM_SEEK_HI_EXCLUSIVE) != 0;
-      uint32_t iv = 0;
-      bool eq = false, prev_eq = false;
-      // inclusive: end = first key > needle (heads <= needle); exclusive: first key >= needle (heads < needle)
-      st = seek_partition(base, p0, t, nb, np, nn, !excl, iv);
-      if (st == ST_OK) st = seek_scan(base, p0, t, iv, nb, np, nn, !excl, end, eq, prev_eq);
-      if (excl ? end > 0 : (end > 0 && prev_eq)) found |= 2;
-    }
-    if (first > end) first = end;  // the two scanners crossed: empty range
-  }
+  if (st == ST_OK) st = seek_block(base, p0, t, SeekBounds{P.lo, P.lo_off, P.hi, P.hi_off}, q, fl, first, end, found);
   P.status[q] = st;
   P.first[q] = st == ST_OK ? first : 0;
   P.end[q] = st == ST_OK ? end : 0;

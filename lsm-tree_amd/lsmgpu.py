@@ -67,6 +67,12 @@ class LsmTableScan(C.Structure):
                 ("global_seqno", C.c_uint64), ("block_count", C.c_uint64)]
 
 
+class LsmRangeResult(C.Structure):
+    _fields_ = [("first_block_off", C.c_void_p), ("first_block_size", C.c_void_p), ("first_item", C.c_void_p),
+                ("last_block_off", C.c_void_p), ("last_block_size", C.c_void_p), ("last_item", C.c_void_p),
+                ("first_block", C.c_void_p), ("last_block", C.c_void_p)]
+
+
 ABI_VERSION = 7
 DECODE_ITEM_START_VALID = 1
 # lsm_decode_tuning.flags / lsm_block_params.flags: take the workspace pool (explicit opt-in)
@@ -214,6 +220,11 @@ def lib():
                                         C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_uint32, C.POINTER(LsmPointResult), C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]
+        if hasattr(L, "lsm_table_range"):  # (variant builds of earlier trees lack it: A/B scripts)
+            L.lsm_table_range.restype = C.c_int
+            L.lsm_table_range.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(LsmTableScan), C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                          C.POINTER(LsmRangeResult), C.c_void_p, C.c_void_p, C.c_void_p]
         L.lsm_materialize_workspace_size.restype = C.c_size_t
         L.lsm_materialize_workspace_size.argtypes = [C.c_uint64]
         L.lsm_materialize_plan.restype = C.c_int
@@ -296,7 +307,7 @@ EXPORTED_SYMBOLS = ["lsm_abi_version", "lsm_status_name", "lsm_last_error", "lsm
                     "lsm_cut_workspace_size", "lsm_cut_blocks_device",
                     "lsm_index_entries_workspace_size", "lsm_index_entries",
                     "lsm_lz4_compress_bound", "lsm_lz4_compress_workspace_size", "lsm_lz4_compress_blocks",
-                    "lsm_table_get"]
+                    "lsm_table_get", "lsm_table_range"]
 
 
 def _check(rc, what):
@@ -567,6 +578,55 @@ def table_get(file, table, needles, needle_off, snapshot, key_hash=None, active=
 
 
 SEEK_LO, SEEK_HI, SEEK_LO_EXCLUSIVE, SEEK_HI_EXCLUSIVE = 1, 2, 4, 8
+
+RANGE_NONE, RANGE_NO_BLOCK, RANGE_EMPTY, RANGE_ROWS = range(4)
+TABLE_RANGE_FIELDS = (("first_block_off", "int64"), ("first_block_size", "int32"), ("first_item", "int32"),
+                      ("last_block_off", "int64"), ("last_block_size", "int32"), ("last_item", "int32"),
+                      ("first_block", "int32"), ("last_block", "int32"), ("outcome", "uint8"), ("status", "int32"))
+
+
+def table_range(file, table, lo, lo_off, hi, hi_off, flags, scan=None, out=None, stream=None):
+    """Batched Table::range bounds (src/table/mod.rs:391-422, the forward drain of
+    src/table/iter.rs:94-293) on a table file image: file = padded uint8 cuda tensor; table = dict
+    with tli_off, tli_size, two_level (and an optional file_len, else the end of the TLI); lo / hi
+    uint8 padded arenas with int64 [n+1] offsets and flags uint8 [n] (SEEK_* bits) as seek().
+    Returns dict of cuda tensors first_block_off / first_block_size / first_item (the first row:
+    its block's handle and its index in the block), last_* (the last row, inclusive), outcome
+    (RANGE_*) and status; rows whose outcome is not RANGE_ROWS keep what the tensors held.
+    out: such a dict to write into.  scan: a dict holding block_off (the table's data-block offsets,
+    int64 [n_blocks + 1], n_blocks taken from scan["n_blocks"] when that is an int) and item_start,
+    as scan_table returns: first_block / last_block are then the two blocks' ordinals, and
+    row_first / row_end the row window [item_start[first_block] + first_item,
+    item_start[last_block] + last_item + 1) of the scan, 0 / 0 where the outcome is not RANGE_ROWS.
+    No host synchronisation."""
+    torch = _torch()
+    n = int(flags.numel())
+    dev = file.device
+    if out is None:
+        out = {f: torch.zeros(max(n, 1), dtype=getattr(torch, dt), device=dev) for f, dt in TABLE_RANGE_FIELDS}
+    file_len = table.get("file_len", table["tli_off"] + table["tli_size"])
+    t = LsmTableScan(table["tli_off"], table["tli_size"], int(bool(table.get("two_level", False))), 0, 0)
+    block_off, n_blocks = None, 0
+    if scan is not None:
+        block_off = scan["block_off"]
+        nb = scan.get("n_blocks")
+        n_blocks = nb if isinstance(nb, int) else int(block_off.numel()) - 1
+    res = LsmRangeResult(*(_ptr(out[f]) if block_off is not None or not f.endswith("_block") else None
+                           for f, _ in TABLE_RANGE_FIELDS[:8]))
+    _check(lib().lsm_table_range(_ptr(file), file_len, C.byref(t), _ptr(lo), _ptr(lo_off), _ptr(hi), _ptr(hi_off),
+                                 _ptr(flags), n, _ptr(block_off), n_blocks, C.byref(res), _ptr(out["outcome"]),
+                                 _ptr(out["status"]), _stream(stream)), "lsm_table_range")
+    if scan is not None:
+        rows = out["outcome"][:n] == RANGE_ROWS
+        start = scan["item_start"].to(torch.int64)
+        # (rows the kernel left alone may hold anything: gather at 0 there)
+        fb = torch.where(rows, out["first_block"][:n].to(torch.int64), 0).clamp_(0, start.numel() - 1)
+        lb = torch.where(rows, out["last_block"][:n].to(torch.int64), 0).clamp_(0, start.numel() - 1)
+        zero = torch.zeros((), dtype=torch.int64, device=dev)
+        out["row_first"] = torch.where(rows, start[fb] + out["first_item"][:n], zero)
+        out["row_end"] = torch.where(rows, start[lb] + out["last_item"][:n] + 1, zero)
+    return out
+
 
 
 def seek(blocks, block_off, n_blocks, query_block, lo, lo_off, hi, hi_off, flags, stream=None):
