@@ -56,6 +56,10 @@
  *                         per block iter.rs:272-277), index_block::Iter::seek / seek_upper
  *                         index_block/iter.rs:25-40 over partition_point_2 block/decoder.rs:210-256,
  *                         TwoLevelBlockIndex's Iter block_index/two_level.rs:78-173
+ *   lsm_table_range_rows_plan / lsm_table_range_rows
+ *                      <- the items Table::range yields  src/table/mod.rs:391-422, iter.rs:272-290
+ *                         (the owned InternalValue with seqno + global_seqno of every row between the two
+ *                         positions of lsm_table_range)
  *   lsm_merge_runs     <- Merger::new / next       src/merge.rs:34-100
  *                         CompactionStream          src/compaction/stream.rs:46-221
  *                         InternalKey Ord           src/key.rs:59-72
@@ -851,6 +855,99 @@ int lsm_table_range(const uint8_t* d_file, uint64_t file_len, const lsm_table_sc
                     const uint64_t* d_data_block_off, uint32_t n_data_blocks,
                     const void* d_out /* const lsm_range_result* */, uint8_t* d_outcome, int32_t* d_status,
                     void* stream);
+
+/* ---- rows of a range in a table (Table::range's items, iter.rs:272-290) ----------
+ * The rows between the positions lsm_table_range reports, as item runs: per query the
+ * owned InternalValues the forward drain yields (key, value, seqno + global_seqno, value
+ * type), appended to an lsm_items-shaped SoA (what lsm_merge_runs takes) at a cursor held
+ * on the device.  Only the data blocks first_block ..= last_block of each query are read,
+ * so a range over several tables is lsm_table_range -> these two calls -> lsm_merge_runs
+ * with nothing downloaded.
+ * Inputs: d_file / file_len / table as lsm_table_range (same buffer rules; of table only
+ * global_seqno is used); d_data_block_off (n_data_blocks + 1 u64, required): the table's
+ * data-block offsets, block b = d_file[off[b] .. off[b+1]); pos: the address of an
+ * lsm_range_positions (a host struct of device arrays [n_queries], passed as const void*,
+ * every field required): lsm_table_range's d_outcome, d_status, first_block, first_item,
+ * last_block and last_item for the same queries and the same d_data_block_off.
+ * Rows of a query: query q is live when status[q] == LSM_OK and outcome[q] ==
+ * LSM_RANGE_ROWS.  Its rows, in file order: items first_item .. of block first_block,
+ * every item of each block between, items ..= last_item of block last_block (items
+ * first_item ..= last_item when the two are one block).  On a table as the writer writes
+ * it this is exactly the forward drain (the condition lsm_table_range states for its row
+ * window); on a table whose data blocks disagree with its index it is still the rows
+ * between the two positions.  Row fields: key = restart-head prefix || suffix, byte for
+ * byte as lsm_materialize_items writes it (the restart head of a window's first row may
+ * lie before the window); value = the payload slice, empty for tombstones; seqno = the
+ * item's seqno + table->global_seqno, wrapping (iter.rs:285); vtype copied.  A query that
+ * is not live gets an empty run and d_row_status[q] = its input status.
+ * Output layout: the cursor exactly as lsm_materialize_items: d_base (device u64[3], NULL
+ * = zeros) = {items, key bytes, value bytes} already in the outputs, d_end (device u64[3],
+ * not d_base itself) = d_base plus this call's totals.  Run q is the rows
+ * [d_run_start[q], d_run_start[q+1]) (n_queries + 1 u64, absolute row indices:
+ * d_run_start[0] = d_base[0], d_run_start[n_queries] = d_end[0]; with a base of 0 it is
+ * the d_run_start of lsm_merge_runs).  Row r's offsets are d_out_key_off[r] /
+ * d_out_val_off[r]; the entry at d_end[0] holds d_end[1] / d_end[2].  No store touches an
+ * arena byte outside [d_base[k], d_end[k]), a seqno or vtype entry outside
+ * [d_base[0], d_end[0]) or an offset entry outside [d_base[0], d_end[0]].  Arenas that
+ * feed lsm_merge_runs need LSM_INPUT_PADDING readable bytes past their caps.
+ * Validation: payload checksums are verified upstream, as for lsm_table_get and
+ * lsm_table_range.  No byte outside d_file[0 .. file_len + LSM_INPUT_PADDING) is read,
+ * whatever the file, the offsets and the positions hold.  first_block > last_block or an
+ * ordinal >= n_data_blocks: LSM_BAD_ARG for that query, no block touched.  Every touched
+ * block is checked in this order: (1) the handle: off[b+1] - off[b] < 33, a handle that
+ * decreases or one ending past file_len: LSM_TRUNCATED; (2) the header fields as
+ * lsm_table_get's load_block: LSM_BAD_MAGIC / LSM_BAD_TYPE, a type other than Data:
+ * LSM_TYPE_MISMATCH, data_length != size - 33: LSM_TRUNCATED, data_length !=
+ * uncompressed_length: LSM_UNSUPPORTED; (3) the trailer: LSM_PARSE; (4) the edge items:
+ * first_item (first block) or last_item (last block) >= the block's item count, or
+ * first_item > last_item in a single block: LSM_BAD_ARG; (5) the records: the WHOLE block
+ * must parse as lsm_decode_blocks requires (every restart interval starts where the
+ * binary index says, the records end at the marker, the count is the trailer's), else
+ * LSM_PARSE, so that the status does not depend on where the window lies in an edge block.
+ * d_row_status[q] = LSM_OK, or the status of the lowest-ordinal touched block that has
+ * one; such a query gets an EMPTY run, all or nothing (the reference's iterator returns
+ * Err at that block and the caller discards the read); other queries are unaffected.
+ * Capacities, without a read-back: block_cap bounds the (query, block) pairs of the call,
+ * row_cap its rows; both size the workspace and the grids (launched for the caps, with
+ * early exit past the device counts: keep them tight), each at most 2^32 - 2.  d_need
+ * (device u64[4]) = {pairs, rows, key bytes, value bytes} of the call.  More pairs than
+ * block_cap: *d_result = LSM_OVERFLOW, only d_need[0] is meaningful, d_end = d_base, every
+ * run empty.  More rows than row_cap: *d_result = LSM_OVERFLOW; d_need, d_end and
+ * d_run_start still hold the real totals.  Else *d_result = LSM_OK.
+ * lsm_table_range_rows (same file, table, offsets, positions, caps, d_base, d_end and
+ * workspace, the workspace left untouched since the plan) writes all rows or none:
+ * *d_result = LSM_OVERFLOW and nothing is written when the plan overflowed, or when
+ * d_end[0] > out_item_cap (the offset arrays hold out_item_cap + 1 entries),
+ * d_end[1] > key_cap or d_end[2] > val_cap.
+ * n_queries == 0: nothing is read, d_end = d_base, LSM_OK.  LSM_BAD_ARG (before any device
+ * work): a NULL required pointer, d_file not 16-byte aligned, a cap above 2^32 - 2, a
+ * workspace below lsm_table_range_rows_workspace_size(n_queries, block_cap, row_cap),
+ * d_end == d_base.  Both calls are asynchronous on `stream`, do no host synchronisation,
+ * have no wait between workgroups and may be captured into a graph on one stream.
+ * Not built: `limit`, the reverse and mixed drains, LZ4 tables, the MVCC read filter. */
+typedef struct lsm_range_positions {
+    const uint8_t* outcome;      /* LSM_RANGE_* */
+    const int32_t* status;
+    const uint32_t* first_block; /* ordinals in d_data_block_off */
+    const uint32_t* first_item;
+    const uint32_t* last_block;
+    const uint32_t* last_item;   /* inclusive */
+} lsm_range_positions;
+size_t lsm_table_range_rows_workspace_size(uint32_t n_queries, uint64_t block_cap, uint64_t row_cap);
+int lsm_table_range_rows_plan(const uint8_t* d_file, uint64_t file_len, const lsm_table_scan* table,
+                              const uint64_t* d_data_block_off, uint32_t n_data_blocks,
+                              const void* pos /* const lsm_range_positions* */, uint32_t n_queries,
+                              uint64_t block_cap, uint64_t row_cap, const uint64_t* d_base,
+                              uint64_t* d_run_start, uint64_t* d_end, uint64_t* d_need, int32_t* d_row_status,
+                              int32_t* d_result, void* d_workspace, size_t workspace_bytes, void* stream);
+int lsm_table_range_rows(const uint8_t* d_file, uint64_t file_len, const lsm_table_scan* table,
+                         const uint64_t* d_data_block_off, uint32_t n_data_blocks,
+                         const void* pos /* const lsm_range_positions* */, uint32_t n_queries,
+                         uint64_t block_cap, uint64_t row_cap, const uint64_t* d_base, const uint64_t* d_end,
+                         void* d_workspace, size_t workspace_bytes, uint64_t* d_out_key_off,
+                         uint64_t* d_out_val_off, uint8_t* d_out_keys, uint64_t key_cap, uint8_t* d_out_vals,
+                         uint64_t val_cap, uint64_t* d_out_seqno, uint8_t* d_out_vtype, uint64_t out_item_cap,
+                         int32_t* d_result, void* stream);
 
 /* ---- merge of sorted runs with compaction GC ----------------------------------
  * CompactionStream::new(Merger::new(runs), gc_seqno_threshold)

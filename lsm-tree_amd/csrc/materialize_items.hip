@@ -18,8 +18,8 @@
 #include <hip/hip_runtime.h>
 
 #include "block_format.hpp"
-#include "gather.hpp"
 #include "host_common.hpp"
+#include "items_gather.hpp"
 #include "lsmgpu.h"
 #include "scan.hpp"
 
@@ -59,7 +59,6 @@ struct MiParams {
 };
 // meta: the row count, the cursor this plan starts at, and whether it fits out_item_cap
 enum { kMiRows = 0, kMiBase = 1, kMiOverflow = 4, kMiMeta = 8 };
-constexpr uint32_t kMiWaves = 4;
 
 __device__ __forceinline__ uint32_t mi_block_count(const MiParams& P) {
   return P.d_n_blocks ? min(*P.d_n_blocks, P.n_blocks) : P.n_blocks;
@@ -121,16 +120,10 @@ __device__ __forceinline__ uint32_t mi_tile_block(const MiParams& P, uint32_t co
   return mi_find_block(P.item_start, b0, max(b0, b1), min(i, R - 1));
 }
 
-// One parsed row as the gather copies it.  A row is rejected (ok = false, all
-// lengths 0) when its block's status is not LSM_OK, the block is not a data or
-// meta block, or a byte range of the row does not lie in the block's payload.
-struct MiRow {
-  const uint8_t* pre;  // prefix_len bytes of the restart head's key
-  const uint8_t* suf;  // key_len bytes
-  const uint8_t* val;
-  uint32_t pl, kl, vl;
-  bool ok;
-};
+// Parsed row i of block b as the gather copies it (MiRow, items_gather.hpp).  A
+// row is rejected (ok = false, all lengths 0) when its block's status is not
+// LSM_OK, the block is not a data or meta block, or a byte range of the row does
+// not lie in the block's payload.
 __device__ __forceinline__ MiRow mi_row(const MiParams& P, uint64_t i, uint32_t b) {
   MiRow r{P.blocks, P.blocks, P.blocks, 0, 0, 0, false};
   const uint64_t s = P.item_start[b], e = P.item_start[b + 1];
@@ -260,95 +253,24 @@ __global__ __launch_bounds__(kScanThreads) void mi_offsets_kernel(MiParams P, bo
   }
 }
 
-// The gather's LDS buffer per wave: half of kGatherBuf, which doubles the waves per
-// CU (the kernel waits on dependent loads: block search, row, source bytes); a
-// tile of 64-byte values still fits when it starts 16-byte aligned.
-constexpr uint32_t kMiBuf = 4096;
-
-// gather_field through the smaller buffer: the tile's span at once when it fits,
-// else its two half tiles one after the other, each through the buffer when it
-// fits and straight to global when not.
-__device__ __forceinline__ void mi_field(const uint8_t* src, uint32_t len, uint8_t* out, uint64_t o, uint64_t o0,
-                                         uint64_t o1, uint32_t nrow, uint8_t* bf, uint32_t lane) {
-  if (o1 == o0) return;
-  if (__ballot(len >= kGatherLong)) {
-    gather_direct(src, len, out + o, lane);
-    return;
-  }
-  const uint32_t pad = (uint32_t)(((uint64_t)(uintptr_t)out + o0) & 15);
-  if (o1 - o0 + pad <= kMiBuf) {
-    lds_put(src, len, bf + (uint32_t)(o - o0) + pad);
-    span_store(out, o0, o1, pad, bf, lane);
-    return;
-  }
-  const uint32_t h = nrow / 2;
-  const uint64_t om = wave_readlane_u64(o, h);
-#pragma unroll
-  for (uint32_t half = 0; half < 2; ++half) {
-    const uint64_t a = half ? om : o0, e = half ? o1 : om;
-    const uint32_t l = (half ? lane >= h : lane < h) ? len : 0;
-    const uint32_t p = (uint32_t)(((uint64_t)(uintptr_t)out + a) & 15);
-    if (e == a) continue;
-    if (e - a + p <= kMiBuf) {
-      lds_put(src, l, bf + (uint32_t)(o - a) + p);
-      span_store(out, a, e, p, bf, lane);
-    } else {
-      gather_direct(src, l, out + o, lane);
-    }
-  }
-}
+// The gather's row source: the parsed SoA of a decode (items_gather.hpp).
+struct MiParsedRows {
+  static constexpr bool kMeta = true;
+  const MiParams& P;
+  uint32_t count, b;
+  __device__ __forceinline__ void locate(uint64_t R, uint64_t i0, uint64_t i) { b = mi_tile_block(P, count, R, i0, i); }
+  __device__ __forceinline__ MiRow row(uint64_t i) const { return mi_row(P, i, b); }
+  __device__ __forceinline__ uint64_t seqno(uint64_t i) const { return P.seqno[i]; }
+  __device__ __forceinline__ uint8_t vtype(uint64_t i) const { return P.vtype[i]; }
+};
 
 __global__ __launch_bounds__(kMiWaves * 64) void mi_gather_kernel(MiParams P) {
   __shared__ __attribute__((aligned(16))) uint8_t buf[kMiWaves][kMiBuf + 32];
-  const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const uint64_t base0 = P.base ? P.base[0] : 0, base1 = P.base ? P.base[1] : 0, base2 = P.base ? P.base[2] : 0;
-  const uint64_t end0 = P.end[0], end1 = P.end[1], end2 = P.end[2];
-  // all rows or none (the caller sized the outputs without a host sync)
-  const bool fits = end0 <= P.item_cap && end1 <= P.key_cap && end2 <= P.val_cap && base0 <= end0 &&
-                    base1 <= end1 && base2 <= end2;
-  if (blockIdx.x == 0 && threadIdx.x == 0) *P.result = fits ? LSM_OK : LSM_OVERFLOW;
-  if (!fits) return;
   const uint32_t count = mi_block_count(P);
-  const uint64_t R = min(mi_row_count(P, count), end0 - base0);
-  const uint64_t i0 = ((uint64_t)blockIdx.x * kMiWaves + w) * 64;
-  if (i0 >= R) return;
-  const uint32_t nrow = (uint32_t)min((uint64_t)64, R - i0);
-  const bool live = lane < nrow;
-  const uint64_t i = i0 + lane;
-  const uint32_t b = mi_tile_block(P, count, R, i0, i);
-  MiRow r{P.blocks, P.blocks, P.blocks, 0, 0, 0, false};
-  uint64_t ko = 0, vo = 0;
-  if (live) {
-    r = mi_row(P, i, b);
-    ko = P.out_key_off[base0 + i];
-    vo = P.out_val_off[base0 + i];
-  }
-  // the tile's output spans [ko0, ko1) and [vo0, vo1): contiguous, rows in order
-  // (64-bit broadcasts go through uint32_t halves: an offset with bit 31 set is not sign-filled)
-  const uint32_t klen = r.pl + r.kl;
-  const uint64_t ko0 = wave_readlane_u64(ko, 0), ko1 = wave_readlane_u64(ko + klen, nrow - 1);
-  const uint64_t vo0 = wave_readlane_u64(vo, 0), vo1 = wave_readlane_u64(vo + r.vl, nrow - 1);
-  // offsets that are not this plan's (a span outside the cursor's range, a row outside its span): no store
-  const bool stray = live && (ko < ko0 || ko + klen > ko1 || vo < vo0 || vo + r.vl > vo1);
-  if (__ballot(stray) || ko0 < base1 || ko1 > end1 || vo0 < base2 || vo1 > end2) return;
-  uint8_t* bf = buf[w];
-  if (ko1 > ko0) {
-    const uint32_t pad = (uint32_t)(((uint64_t)(uintptr_t)P.out_keys + ko0) & 15);
-    if (__ballot(r.pl >= kGatherLong || r.kl >= kGatherLong) || ko1 - ko0 + pad > kMiBuf) {
-      gather_direct(r.pre, r.pl, P.out_keys + ko, lane);
-      gather_direct(r.suf, r.kl, P.out_keys + ko + r.pl, lane);
-    } else {
-      uint8_t* d = bf + (uint32_t)(ko - ko0) + pad;
-      lds_put(r.pre, r.pl, d);
-      lds_put(r.suf, r.kl, d + r.pl);
-      span_store(P.out_keys, ko0, ko1, pad, bf, lane);
-    }
-  }
-  mi_field(r.val, r.vl, P.out_vals, vo, vo0, vo1, nrow, bf, lane);
-  if (live) {
-    gstore(P.out_seqno, base0 + i, (uint64_t)(r.ok ? P.seqno[i] : 0));
-    gstore(P.out_vtype, base0 + i, (uint8_t)(r.ok ? P.vtype[i] : 0));
-  }
+  MiParsedRows S{P, count, 0};
+  const ItemsOut O{P.base,    P.end,      P.out_key_off, P.out_val_off, P.item_cap,  P.key_cap,
+                   P.val_cap, P.out_keys, P.out_vals,    P.out_seqno,   P.out_vtype, P.result};
+  items_gather_tile(S, O, mi_row_count(P, count), P.blocks, buf);
 }
 
 // The plan's workspace: byte offsets of its regions, in layout order, and their sum.

@@ -73,6 +73,11 @@ class LsmRangeResult(C.Structure):
                 ("first_block", C.c_void_p), ("last_block", C.c_void_p)]
 
 
+class LsmRangePositions(C.Structure):  # lsm_range_positions: lsm_table_range's outputs, read by lsm_table_range_rows
+    _fields_ = [("outcome", C.c_void_p), ("status", C.c_void_p), ("first_block", C.c_void_p),
+                ("first_item", C.c_void_p), ("last_block", C.c_void_p), ("last_item", C.c_void_p)]
+
+
 ABI_VERSION = 7
 DECODE_ITEM_START_VALID = 1
 # lsm_decode_tuning.flags / lsm_block_params.flags: take the workspace pool (explicit opt-in)
@@ -225,6 +230,18 @@ def lib():
             L.lsm_table_range.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(LsmTableScan), C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                           C.POINTER(LsmRangeResult), C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "lsm_table_range_rows"):  # (variant builds of earlier trees lack it: A/B scripts)
+            L.lsm_table_range_rows_workspace_size.restype = C.c_size_t
+            L.lsm_table_range_rows_workspace_size.argtypes = [C.c_uint32, C.c_uint64, C.c_uint64]
+            rr_inputs = [C.c_void_p, C.c_uint64, C.POINTER(LsmTableScan), C.c_void_p, C.c_uint32,
+                         C.POINTER(LsmRangePositions), C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]  # .. d_base
+            L.lsm_table_range_rows_plan.restype = C.c_int
+            L.lsm_table_range_rows_plan.argtypes = rr_inputs + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                                C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+            L.lsm_table_range_rows.restype = C.c_int
+            L.lsm_table_range_rows.argtypes = rr_inputs + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                           C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                           C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.lsm_materialize_workspace_size.restype = C.c_size_t
         L.lsm_materialize_workspace_size.argtypes = [C.c_uint64]
         L.lsm_materialize_plan.restype = C.c_int
@@ -307,7 +324,8 @@ EXPORTED_SYMBOLS = ["lsm_abi_version", "lsm_status_name", "lsm_last_error", "lsm
                     "lsm_cut_workspace_size", "lsm_cut_blocks_device",
                     "lsm_index_entries_workspace_size", "lsm_index_entries",
                     "lsm_lz4_compress_bound", "lsm_lz4_compress_workspace_size", "lsm_lz4_compress_blocks",
-                    "lsm_table_get", "lsm_table_range"]
+                    "lsm_table_get", "lsm_table_range",
+                    "lsm_table_range_rows_workspace_size", "lsm_table_range_rows_plan", "lsm_table_range_rows"]
 
 
 def _check(rc, what):
@@ -626,6 +644,153 @@ def table_range(file, table, lo, lo_off, hi, hi_off, flags, scan=None, out=None,
         out["row_first"] = torch.where(rows, start[fb] + out["first_item"][:n], zero)
         out["row_end"] = torch.where(rows, start[lb] + out["last_item"][:n] + 1, zero)
     return out
+
+
+def table_block_offsets(file, table):
+    """The data-block offsets of a table (int64 cuda [n_blocks + 1], what table_range takes as
+    scan["block_off"] and table_range_rows as block_off) from its block index alone, for a reader
+    that never scanned the table: the TLI's entries, or, when table["two_level"], the entries of
+    the partitions the TLI names, decoded as index blocks (decode_blocks, which verifies them).
+    table as table_range takes it.  Raises LsmError when an index block does not decode or the
+    handles are not contiguous from 0 (the layout a scan reads back to back).  Synchronises."""
+    import numpy as np
+    torch = _torch()
+    dev = file.device
+    file_len = table.get("file_len", table["tli_off"] + table["tli_size"])
+
+    def entries(handles):
+        """[(off, size)] of index blocks -> the handles their entries hold, in order."""
+        out, i = [], 0
+        while i < len(handles):  # one decode per run of blocks that lie back to back
+            j = i + 1
+            while j < len(handles) and handles[j][0] == handles[j - 1][0] + handles[j - 1][1]:
+                j += 1
+            run = handles[i:j]
+            if any(size < LSM_HEADER_LEN for _, size in run) or run[-1][0] + run[-1][1] > file_len:
+                raise LsmError("table_block_offsets: an index block's handle does not lie in the file")
+            off = torch.tensor([h[0] for h in run] + [run[-1][0] + run[-1][1]], dtype=torch.int64, device=dev)
+            cap = sum(size for _, size in run) // 5 + len(run)  # (an index record takes 5 bytes or more)
+            d = decode_blocks(file, off, len(run), expect_type=BLOCK_INDEX, item_cap=cap,
+                              fields=["handle_off", "val_len"])
+            status = d["status"][:len(run)].cpu().numpy()
+            if status.any():
+                raise LsmError(f"table_block_offsets: index block status {STATUS.get(int(status.max()), '?')}")
+            n = int(d["item_start"][len(run)].item())
+            out += zip(d["handle_off"][:n].cpu().tolist(), d["val_len"][:n].cpu().numpy().view(np.uint32).tolist())
+            i = j
+        return out
+
+    handles = entries([(table["tli_off"], table["tli_size"])])
+    if table.get("two_level", False):
+        handles = entries(handles)
+    off = np.zeros(len(handles) + 1, np.int64)
+    for i, (o, size) in enumerate(handles):
+        if o != off[i]:
+            raise LsmError(f"table_block_offsets: data block {i} at {o}, not contiguous from 0")
+        off[i + 1] = o + size
+    if off[-1] > file_len:
+        raise LsmError("table_block_offsets: the data blocks end past the file")
+    return torch.from_numpy(off).to(dev)
+
+
+RANGE_ROWS_AUTO_PAIRS = 1 << 22
+
+
+def table_range_rows(file, table, positions, block_off, base=None, into=None, caps=None, stream=None,
+                     n_queries=None):
+    """lsm_table_range_rows_plan + lsm_table_range_rows: the rows between the positions of
+    table_range, as item runs.  file / table as table_range (table["global_seqno"], default 0, is
+    added to every seqno); positions: the dict table_range(..., scan={"block_off": block_off})
+    returned (outcome, status, first_block, first_item, last_block, last_item are read);
+    block_off: the table's data-block offsets, int64 cuda [n_blocks + 1] (scan_table's,
+    write_table's or table_block_offsets'); n_queries: default the positions' length.
+    Returns the device lsm_items dict (keys, key_off, vals, val_off, seqno, vtype; padded arenas)
+    that merge_runs takes, plus run_start (int64 [n + 1]: run q is the rows
+    [run_start[q], run_start[q+1]), absolute), row_status (int32 [n]), end (int64 [3]: base plus
+    this call's {rows, key bytes, value bytes}), need (int64 [4]: {pairs, rows, key bytes, value
+    bytes}), result and plan_result (int32 [1]: LSM_OK / LSM_OVERFLOW of the rows call and of the
+    plan).  base: device int64 [3] cursor the rows are appended at (None = zeros; needs `into`).
+    caps = (pairs, rows, key bytes, value bytes[, items]), in need's order: the call's block_cap
+    and row_cap and the outputs' capacities; no host synchronisation, nothing trimmed.  into: an
+    items dict (as this call or materialize_items returned it) to append to in place; its
+    capacities are its tensors' (the arenas' less LSM_INPUT_PADDING) unless caps narrows them.
+    caps=None: a sizing plan with row_cap 0 and block_cap n_queries x n_blocks runs first and
+    need is read back once, the only host synchronisation (above RANGE_ROWS_AUTO_PAIRS possible
+    pairs the pair count is read back first, by itself); without `into` the outputs are
+    allocated for need and trimmed to the rows."""
+    torch = _torch()
+    dev = file.device
+    n = int(positions["outcome"].numel()) if n_queries is None else int(n_queries)
+    n_blocks = int(block_off.numel()) - 1
+    file_len = table.get("file_len", table["tli_off"] + table["tli_size"])
+    t = LsmTableScan(table["tli_off"], table["tli_size"], int(bool(table.get("two_level", False))),
+                     table.get("global_seqno", 0) & (2 ** 64 - 1), 0)
+    ps = LsmRangePositions(*(_ptr(positions[f]) for f in ("outcome", "status", "first_block", "first_item",
+                                                          "last_block", "last_item")))
+    if base is not None and into is None:
+        raise LsmError("table_range_rows: a base needs `into` (the outputs it already fills)")
+    st = _stream(stream)
+    cur = torch.cuda.current_stream(dev) if stream is None else stream
+    run_start = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    row_status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    end = torch.zeros(3, dtype=torch.int64, device=dev)
+    need = torch.zeros(4, dtype=torch.int64, device=dev)
+    result = torch.zeros(1, dtype=torch.int32, device=dev)
+    plan_result = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def plan(block_cap, row_cap):
+        ws = torch.empty(lib().lsm_table_range_rows_workspace_size(n, block_cap, row_cap), dtype=torch.uint8,
+                         device=dev)
+        _check(lib().lsm_table_range_rows_plan(_ptr(file), file_len, C.byref(t), _ptr(block_off), n_blocks,
+                                               C.byref(ps), n, block_cap, row_cap, _ptr(base), _ptr(run_start),
+                                               _ptr(end), _ptr(need), _ptr(row_status), _ptr(plan_result), _ptr(ws),
+                                               ws.numel(), st), "lsm_table_range_rows_plan")
+        ws.record_stream(cur)
+        return ws
+
+    def read_need():
+        if stream is not None:
+            stream.synchronize()
+        return need.cpu().tolist()
+
+    trim = None
+    explicit = caps is not None
+    if caps is None:
+        bound = n * n_blocks
+        if bound > RANGE_ROWS_AUTO_PAIRS:
+            plan(0, 0)
+            bound = read_need()[0]
+        plan(bound, 0)
+        pairs, rows, key_bytes, val_bytes = read_need()
+        caps = (pairs, rows, key_bytes, val_bytes)
+        if into is None:
+            trim = rows
+    block_cap, row_cap = int(caps[0]), int(caps[1])
+    if into is not None:
+        dst = into
+        item_cap = into["seqno"].numel()
+        key_cap, val_cap = into["keys"].numel() - LSM_INPUT_PADDING, into["vals"].numel() - LSM_INPUT_PADDING
+        if explicit:
+            key_cap, val_cap = min(key_cap, int(caps[2])), min(val_cap, int(caps[3]))
+            if len(caps) > 4:
+                item_cap = min(item_cap, int(caps[4]))
+    else:
+        item_cap = int(caps[4]) if len(caps) > 4 else row_cap
+        key_cap, val_cap = int(caps[2]), int(caps[3])
+        dst = _mi_alloc(dev, item_cap, key_cap, val_cap)
+    ws = plan(block_cap, row_cap)
+    _check(lib().lsm_table_range_rows(_ptr(file), file_len, C.byref(t), _ptr(block_off), n_blocks, C.byref(ps), n,
+                                      block_cap, row_cap, _ptr(base), _ptr(end), _ptr(ws), ws.numel(),
+                                      _ptr(dst["key_off"]), _ptr(dst["val_off"]), _ptr(dst["keys"]), key_cap,
+                                      _ptr(dst["vals"]), val_cap, _ptr(dst["seqno"]), _ptr(dst["vtype"]), item_cap,
+                                      _ptr(result), st), "lsm_table_range_rows")
+    items = {f: dst[f] for f in ("keys", "key_off", "vals", "val_off", "seqno", "vtype")}
+    if trim is not None:
+        items.update(key_off=dst["key_off"][:trim + 1], val_off=dst["val_off"][:trim + 1],
+                     seqno=dst["seqno"][:trim], vtype=dst["vtype"][:trim])
+    items.update(run_start=run_start, row_status=row_status[:n], end=end, need=need, result=result,
+                 plan_result=plan_result)
+    return items
 
 
 
