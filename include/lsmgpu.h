@@ -64,6 +64,8 @@
  *                         CompactionStream          src/compaction/stream.rs:46-221
  *                         InternalKey Ord           src/key.rs:59-72
  *                         (as composed in compaction/worker.rs:149-182,389-390)
+ *   lsm_merge_read     <- TreeIter::create_range   src/range.rs:99-235 (seqno_filter range.rs:22-24,
+ *                         Merger::new, MvccStream::next src/mvcc_stream.rs:45-52, the tombstone filter)
  *   lsm_bloom_shape    <- BloomConstructionPolicy::init  src/table/filter/mod.rs:25-34
  *   lsm_hash64_keys    <- FullFilterWriter::register_key src/table/writer/filter/full.rs:47-50
  *   lsm_bloom_build    <- standard_bloom Builder set_with_hash + build  builder.rs:33-53,154-170
@@ -924,7 +926,8 @@ int lsm_table_range(const uint8_t* d_file, uint64_t file_len, const lsm_table_sc
  * workspace below lsm_table_range_rows_workspace_size(n_queries, block_cap, row_cap),
  * d_end == d_base.  Both calls are asynchronous on `stream`, do no host synchronisation,
  * have no wait between workgroups and may be captured into a graph on one stream.
- * Not built: `limit`, the reverse and mixed drains, LZ4 tables, the MVCC read filter. */
+ * Not built: `limit`, the reverse and mixed drains, LZ4 tables.  The MVCC read filter over
+ * the rows of several tables is lsm_merge_read. */
 typedef struct lsm_range_positions {
     const uint8_t* outcome;      /* LSM_RANGE_* */
     const int32_t* status;
@@ -987,6 +990,63 @@ int lsm_merge_runs(const lsm_items* d_in, const uint64_t* d_run_start, uint32_t 
                    uint8_t* d_out_vals, uint64_t* d_out_val_off,
                    uint64_t* d_out_seqno, uint8_t* d_out_vtype,
                    uint32_t* d_out_src, uint64_t* d_n_out, int32_t* d_status,
+                   void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ---- read merge: the snapshot read of per-query item runs ------------------------
+ * What a reader gets from TreeIter::create_range (range.rs:99-235), for n_groups
+ * queries at once: every source filtered by seqno_filter(item.seqno, snapshot)
+ * (range.rs:22-24), Merger::new over the sources, MvccStream::new (the first item of
+ * each user key, the rest drained, mvcc_stream.rs:45-52), then the tombstone filter.
+ * The step after lsm_table_range_rows: a range over several tables is lsm_table_range
+ * -> lsm_table_range_rows per table -> this call, with nothing downloaded.
+ * Input: as lsm_merge_runs (d_in holds every run back to back, both arenas readable
+ * LSM_INPUT_PADDING bytes past their end, n_items <= 2^32 - 2), with
+ * n_sources * n_groups runs: run s * n_groups + g is source s of group (query) g,
+ * source-major, the order n_sources chained lsm_table_range_rows calls over the same
+ * n_groups queries write when call s is given d_run_start + s * n_groups (its last
+ * entry is the next call's first).  d_run_start: n_sources * n_groups + 1 device u64,
+ * first 0, last n_items, non-decreasing; empty runs are normal.  Each run is sorted in
+ * InternalKey order (equal neighbours are accepted).
+ * Per group g, with snap = d_group_seqno ? d_group_seqno[g] : snapshot_seqno:
+ * (1) an item is visible iff seqno < snap (seqno == snap is not); (2) the visible items
+ * of the group's runs are merged in InternalKey order, items with equal (key, seqno)
+ * lower source first, as lsm_merge_runs; (3) of each user key only the first item of
+ * that order is kept (MvccStream::next); (4) unless LSM_MERGE_READ_KEEP_TOMBSTONES is
+ * set, a kept Tombstone or WeakTombstone is dropped (Indirection is kept).  The flag is
+ * for a caller who merges the result with sources that stay on the host (memtables):
+ * the tombstones must shadow older versions there.  MvccStream::next_back yields the
+ * same items in reverse (mvcc_stream.rs test_reverse!), so the output serves both
+ * directions of the iterator.
+ * Output: group g's rows are [d_out_group_start[g], d_out_group_start[g+1])
+ * (n_groups + 1 device u64, the first 0, the last the total), laid out as
+ * lsm_merge_runs' output items; offset entries 0 ..= total are written, d_out_src[j]
+ * (may be NULL) is the input index of row j, seqnos are copied unchanged.  Nothing is
+ * stored past row total, past offset entry total or past the arenas' [0, last offset).
+ * The caller sizes the outputs for the input, as for lsm_merge_runs.  Outputs must not
+ * overlap inputs.
+ * d_status[g] (n_groups device i32), per group, other groups unaffected: when
+ * d_in_status (NULL or n_sources * n_groups device i32, the d_row_status of the rows
+ * calls, in run order) holds a non-zero entry for a source of the group, that entry of
+ * the lowest such source, and the group's output is empty (the reference's iterator
+ * returns Err and the read is discarded); else LSM_BAD_ARG and an empty output when a
+ * run of the group is not sorted; a malformed d_run_start gives every group
+ * LSM_BAD_ARG and every d_out_group_start entry 0; else LSM_OK.
+ * LSM_BAD_ARG before any device work: a NULL required pointer, n_sources outside
+ * 1 ..= LSM_MERGE_MAX_RUNS, n_groups == 0 with n_items != 0, n_sources * n_groups or
+ * n_items above 2^32 - 2, an unknown flag bit, a workspace below
+ * lsm_merge_read_workspace_size(n_items, n_groups, n_sources).  n_groups == 0 writes
+ * d_out_group_start[0] = 0.  Asynchronous on `stream`: no host synchronisation, no
+ * wait between workgroups; may be captured into a graph on one stream.
+ * Not built: a per-query `limit`, memtable sources, RunReader's table selection. */
+#define LSM_MERGE_READ_KEEP_TOMBSTONES 1u
+size_t lsm_merge_read_workspace_size(uint64_t n_items, uint32_t n_groups, uint32_t n_sources);
+int lsm_merge_read(const lsm_items* d_in, const uint64_t* d_run_start,
+                   uint32_t n_groups, uint32_t n_sources,
+                   uint64_t snapshot_seqno, const uint64_t* d_group_seqno /* NULL or [n_groups] */,
+                   const int32_t* d_in_status /* NULL or [n_sources * n_groups] */, uint32_t flags,
+                   uint8_t* d_out_keys, uint64_t* d_out_key_off, uint8_t* d_out_vals, uint64_t* d_out_val_off,
+                   uint64_t* d_out_seqno, uint8_t* d_out_vtype, uint32_t* d_out_src /* may be NULL */,
+                   uint64_t* d_out_group_start /* [n_groups + 1] */, int32_t* d_status /* [n_groups] */,
                    void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* ---- table write side: block cut and block index on the device -------------------

@@ -19,6 +19,8 @@
 //                           values (>= kGatherLong) copied by the whole wave
 // Tie rule: of two items with equal (key, seqno) the lower run comes first
 // (lower bound in higher runs, upper bound in lower runs).
+// lsm_merge_read (the reader's merge of per-query runs, range.rs:99-235) shares
+// the heads, scan and gather stages; its own kernels are listed further down.
 #include <hip/hip_runtime.h>
 
 #include "device_common.hpp"
@@ -371,6 +373,162 @@ struct MergeWorkspace {
   }
 };
 
+// ------------------------------------------------- read merge (lsm_merge_read)
+// Q independent merges of S runs each, with the reader's rule in place of the
+// compaction's (range.rs:99-235: seqno_filter per source, Merger, MvccStream,
+// the tombstone filter).  Run s * n_groups + g is source s of group g.  The heads
+// kernel, the three scans and the gather kernel are the ones above (thr = 0,
+// flags = 0); the kernels here stand where setup, check, split + rank and gc do:
+//   read_runs_kernel    lane per run: run_start checked (a fault is the whole call's)
+//   read_groups_kernel  lane per group: the group's item total, d_in_status folded
+//                       into d_status[g]; then a scan gives the groups' bases
+//   read_check_kernel   lane per item: item i - 1 <= item i inside a run; a fault
+//                       is its group's (d_status[g], one value, plain store)
+//   read_rank_kernel    lane per item: searched in the group's other runs, whole
+//   read_rule_kernel    lane per merged position: visible, first visible of its
+//                       key in its group, not a tombstone
+//   read_starts_kernel  lane per group: d_out_group_start[g] = oidx[gbase[g]]
+struct ReadParams {
+  MergeParams M;  // n_runs = n_sources * n_groups, status = d_status [n_groups], n_out = &d_out_group_start[n_groups]
+  uint32_t n_groups, n_sources;
+  uint64_t snapshot;
+  const uint64_t* group_seqno;  // or null
+  const int32_t* in_status;     // or null
+  uint32_t keep_tombstones;
+  uint64_t* out_group_start;
+  // workspace
+  uint32_t* bad;    // [1] a run_start fault (zeroed by the call before read_runs_kernel)
+  uint32_t* glen;   // [n_groups] items of each group
+  uint32_t* gbase;  // [n_groups + 1] first merged position of each group
+};
+
+__global__ __launch_bounds__(256) void read_runs_kernel(ReadParams R) {
+  const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (r >= R.M.n_runs) return;
+  const uint64_t s = gload(R.M.run_start, r), e = gload(R.M.run_start, r + 1);
+  const bool ok = s <= e && e <= R.M.n && (r != 0 || s == 0) && (r + 1 != R.M.n_runs || e == R.M.n);
+  if (!ok) gstore(R.bad, 0, 1u);
+}
+
+__global__ __launch_bounds__(256) void read_groups_kernel(ReadParams R) {
+  const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= R.n_groups) return;
+  uint64_t total = 0;
+  int32_t fault = LSM_OK;
+  if (gload(R.bad, 0)) {
+    fault = LSM_BAD_ARG;
+  } else {
+    for (uint32_t s = 0; s < R.n_sources; ++s) {
+      const uint64_t r = (uint64_t)s * R.n_groups + g;
+      total += gload(R.M.run_start, r + 1) - gload(R.M.run_start, r);
+      if (R.in_status && fault == LSM_OK) fault = gload(R.in_status, r);  // the lowest source's
+    }
+  }
+  gstore(R.glen, g, (uint32_t)total);
+  gstore(R.M.status, g, fault);
+}
+
+struct BaseOut {  // scan of the group totals
+  uint32_t* gbase;
+  __device__ void operator()(uint64_t g, uint64_t prefix) const { gbase[g] = (uint32_t)prefix; }
+};
+
+__global__ __launch_bounds__(256) void read_check_kernel(ReadParams R) {
+  if (gload(R.bad, 0)) return;
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= R.M.n || i == 0) return;
+  const uint32_t r = upper_slot(R.M.run_start, R.M.n_runs, i);
+  if (i == gload(R.M.run_start, r)) return;  // first item of its run
+  const uint32_t g = r % R.n_groups;
+  if (gload(R.M.status, g) != LSM_OK) return;  // an input status stands; an unsorted mark is already there
+  const MergeItem x = load_item(R.M, i);
+  if (cmp_probe(R.M, i - 1, x) > 0) gstore(R.M.status, g, (int32_t)LSM_BAD_ARG);
+}
+
+__global__ __launch_bounds__(256) void read_rank_kernel(ReadParams R) {
+  if (gload(R.bad, 0)) return;
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= R.M.n) return;
+  const uint32_t r = upper_slot(R.M.run_start, R.M.n_runs, i);
+  const uint32_t s = r / R.n_groups, g = r % R.n_groups;
+  if (gload(R.M.status, g) != LSM_OK) return;  // nothing of a faulted group is emitted
+  const MergeItem x = load_item(R.M, i);
+  uint64_t pos = (uint64_t)gload(R.gbase, g) + (i - gload(R.M.run_start, r));
+  for (uint32_t q = 0; q < R.n_sources; ++q) {
+    if (q == s) continue;
+    const uint64_t qr = (uint64_t)q * R.n_groups + g;
+    const uint64_t qs = gload(R.M.run_start, qr);
+    const uint32_t qlen = (uint32_t)(gload(R.M.run_start, qr + 1) - qs);
+    pos += rank_in(R.M, x, qs, 0, qlen, q < s);
+  }
+  if (pos < R.M.n) gstore(R.M.perm, pos, (uint32_t)i);
+}
+
+// The per-item form of seqno_filter + MvccStream::next + the tombstone filter
+// (range.rs:22-24,215-228, mvcc_stream.rs:45-52): seqnos do not increase inside a
+// key, so a key's invisible versions come first and position j is the key's
+// emitted head iff it is visible and its predecessor in the group is another
+// key or invisible.
+__global__ __launch_bounds__(256) void read_rule_kernel(ReadParams R) {
+  const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= R.M.n) return;
+  bool keep = false;
+  uint32_t kl = 0, vl = 0;
+  if (!gload(R.bad, 0)) {
+    const uint32_t g = upper_slot(R.gbase, R.n_groups, j);
+    if (gload(R.M.status, g) == LSM_OK) {
+      const uint64_t snap = R.group_seqno ? gload(R.group_seqno, g) : R.snapshot;
+      const uint32_t i = gload(R.M.perm, j);
+      const MergeItem x = load_item(R.M, i);
+      if (x.seq < snap) {
+        bool head = j == gload(R.gbase, g);
+        if (!head) {
+          const MergeItem y = load_item(R.M, gload(R.M.perm, j - 1));
+          head = !(y.seq < snap) || !same_user_key(y, x);
+        }
+        const uint32_t t = gload(R.M.vtype, (uint64_t)i);
+        const bool tomb = t == LSM_TOMBSTONE || t == LSM_WEAK_TOMBSTONE;
+        keep = head && (!tomb || R.keep_tombstones);
+      }
+      if (keep) {
+        kl = (uint32_t)x.len;
+        vl = (uint32_t)(gload(R.M.val_off, (uint64_t)i + 1) - gload(R.M.val_off, (uint64_t)i));
+      }
+    }
+  }
+  gstore(R.M.keep, j, keep ? 1u : 0u);
+  gstore(R.M.klen, j, kl);
+  gstore(R.M.vlen, j, vl);
+}
+
+__global__ __launch_bounds__(256) void read_starts_kernel(ReadParams R) {
+  const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= R.n_groups) return;
+  gstore(R.out_group_start, g, (uint64_t)gload(R.M.oidx, (uint64_t)gload(R.gbase, g)));
+}
+
+struct MergeReadWorkspace {
+  size_t bad, heads, perm, keep, oidx, klen, vlen, koff, voff, tiles, glen, gbase, total;
+  MergeReadWorkspace(uint64_t n_items, uint32_t n_groups, uint32_t /*n_sources*/) {
+    const uint64_t n = n_items ? n_items : 1;
+    const uint64_t q = n_groups ? n_groups : 1;
+    Carver c;
+    bad = c.take(4);
+    heads = c.take(n * 16);
+    perm = c.take(n * 4);
+    keep = c.take(n * 4);
+    oidx = c.take((n + 1) * 4);
+    klen = c.take(n * 4);
+    vlen = c.take(n * 4);
+    koff = c.take((n + 1) * 8);
+    voff = c.take((n + 1) * 8);
+    tiles = c.take(scan_tiles((n > q ? n : q) + 1) * 8);
+    glen = c.take(q * 4);
+    gbase = c.take((q + 1) * 4);
+    total = c.total();
+  }
+};
+
 }  // namespace lsmgpu
 
 using namespace lsmgpu;
@@ -451,6 +609,110 @@ extern "C" int lsm_merge_runs(const lsm_items* d_in, const uint64_t* d_run_start
   if (e == hipSuccess) e = launch_excl_scan(P.klen, n, tiles, OffOut{P.koff, d_out_key_off, P.oidx, n}, st);
   if (e == hipSuccess) e = launch_excl_scan(P.vlen, n, tiles, OffOut{P.voff, d_out_val_off, P.oidx, n}, st);
   if (e != hipSuccess) return hip_status(e, where);
+  hipLaunchKernelGGL(merge_gather_kernel, dim3((uint32_t)((n + kMergeWaves * 64 - 1) / (kMergeWaves * 64))),
+                     dim3(kMergeWaves * 64), 0, st, P);
+  return hip_status(hipGetLastError(), where);
+}
+
+extern "C" size_t lsm_merge_read_workspace_size(uint64_t n_items, uint32_t n_groups, uint32_t n_sources) {
+  return MergeReadWorkspace(n_items, n_groups, n_sources).total;
+}
+
+extern "C" int lsm_merge_read(const lsm_items* d_in, const uint64_t* d_run_start, uint32_t n_groups,
+                              uint32_t n_sources, uint64_t snapshot_seqno, const uint64_t* d_group_seqno,
+                              const int32_t* d_in_status, uint32_t flags, uint8_t* d_out_keys,
+                              uint64_t* d_out_key_off, uint8_t* d_out_vals, uint64_t* d_out_val_off,
+                              uint64_t* d_out_seqno, uint8_t* d_out_vtype, uint32_t* d_out_src,
+                              uint64_t* d_out_group_start, int32_t* d_status, void* d_workspace,
+                              size_t workspace_bytes, void* stream) {
+  if (!d_in || !d_run_start || !d_out_group_start || !d_status || !d_workspace) return LSM_BAD_ARG;
+  if (n_sources < 1 || n_sources > LSM_MERGE_MAX_RUNS) return LSM_BAD_ARG;
+  if (flags & ~LSM_MERGE_READ_KEEP_TOMBSTONES) return LSM_BAD_ARG;
+  const uint64_t n = d_in->n_items;
+  if (n > 0xFFFFFFFEULL) return LSM_BAD_ARG;
+  if (n_groups == 0 && n != 0) return LSM_BAD_ARG;
+  const uint64_t n_runs = (uint64_t)n_sources * n_groups;
+  if (n_runs > 0xFFFFFFFEULL) return LSM_BAD_ARG;
+  if (!d_in->keys || !d_in->key_off || !d_in->vals || !d_in->val_off || !d_in->seqno || !d_in->vtype)
+    return LSM_BAD_ARG;
+  if (!d_out_keys || !d_out_key_off || !d_out_vals || !d_out_val_off || !d_out_seqno || !d_out_vtype)
+    return LSM_BAD_ARG;
+  const MergeReadWorkspace W(n, n_groups, n_sources);
+  if (workspace_bytes < W.total) return LSM_BAD_ARG;
+  const hipStream_t st = (hipStream_t)stream;
+  const char* where = "lsm_merge_read";
+  hipError_t e;
+  if (n_groups == 0) {  // no query: the one entry of d_out_group_start
+    if ((e = hipMemsetAsync(d_out_group_start, 0, 8, st)) != hipSuccess) return hip_status(e, where);
+    return LSM_OK;
+  }
+  uint8_t* ws = (uint8_t*)d_workspace;
+  ReadParams R;
+  MergeParams& P = R.M;
+  P.keys = d_in->keys;
+  P.key_off = d_in->key_off;
+  P.vals = d_in->vals;
+  P.val_off = d_in->val_off;
+  P.seqno = d_in->seqno;
+  P.vtype = d_in->vtype;
+  P.n = n;
+  P.run_start = d_run_start;
+  P.n_runs = (uint32_t)n_runs;
+  P.thr = 0;
+  P.flags = 0;
+  P.out_keys = d_out_keys;
+  P.out_key_off = d_out_key_off;
+  P.out_vals = d_out_vals;
+  P.out_val_off = d_out_val_off;
+  P.out_seqno = d_out_seqno;
+  P.out_vtype = d_out_vtype;
+  P.out_src = d_out_src;
+  P.n_out = d_out_group_start + n_groups;
+  P.status = d_status;
+  P.hdr = nullptr;
+  P.heads = (uint64_t*)(ws + W.heads);
+  P.perm = (uint32_t*)(ws + W.perm);
+  P.keep = (uint32_t*)(ws + W.keep);
+  P.oidx = (uint32_t*)(ws + W.oidx);
+  P.klen = (uint32_t*)(ws + W.klen);
+  P.vlen = (uint32_t*)(ws + W.vlen);
+  P.koff = (uint64_t*)(ws + W.koff);
+  P.voff = (uint64_t*)(ws + W.voff);
+  P.table = nullptr;
+  R.n_groups = n_groups;
+  R.n_sources = n_sources;
+  R.snapshot = snapshot_seqno;
+  R.group_seqno = d_group_seqno;
+  R.in_status = d_in_status;
+  R.keep_tombstones = flags & LSM_MERGE_READ_KEEP_TOMBSTONES;
+  R.out_group_start = d_out_group_start;
+  R.bad = (uint32_t*)(ws + W.bad);
+  R.glen = (uint32_t*)(ws + W.glen);
+  R.gbase = (uint32_t*)(ws + W.gbase);
+  uint64_t* tiles = (uint64_t*)(ws + W.tiles);
+  const uint32_t group_blocks = (uint32_t)(((uint64_t)n_groups + 255) / 256);
+  if ((e = hipMemsetAsync(R.bad, 0, 4, st)) != hipSuccess) return hip_status(e, where);
+  hipLaunchKernelGGL(read_runs_kernel, dim3((uint32_t)((n_runs + 255) / 256)), dim3(256), 0, st, R);
+  hipLaunchKernelGGL(read_groups_kernel, dim3(group_blocks), dim3(256), 0, st, R);
+  if (n == 0) {  // nothing to merge: the statuses stand, every start and the first offsets are 0
+    e = hipMemsetAsync(d_out_group_start, 0, ((size_t)n_groups + 1) * 8, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_out_key_off, 0, 8, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_out_val_off, 0, 8, st);
+    if (e != hipSuccess) return hip_status(e, where);
+    return hip_status(hipGetLastError(), where);
+  }
+  const uint32_t item_blocks = (uint32_t)((n + 255) / 256);
+  e = launch_excl_scan(R.glen, n_groups, tiles, BaseOut{R.gbase}, st);
+  if (e != hipSuccess) return hip_status(e, where);
+  hipLaunchKernelGGL(merge_heads_kernel, dim3(item_blocks), dim3(256), 0, st, P);
+  hipLaunchKernelGGL(read_check_kernel, dim3(item_blocks), dim3(256), 0, st, R);
+  hipLaunchKernelGGL(read_rank_kernel, dim3(item_blocks), dim3(256), 0, st, R);
+  hipLaunchKernelGGL(read_rule_kernel, dim3(item_blocks), dim3(256), 0, st, R);
+  e = launch_excl_scan(P.keep, n, tiles, KeepOut{P.oidx, P.n_out, n}, st);
+  if (e == hipSuccess) e = launch_excl_scan(P.klen, n, tiles, OffOut{P.koff, d_out_key_off, P.oidx, n}, st);
+  if (e == hipSuccess) e = launch_excl_scan(P.vlen, n, tiles, OffOut{P.voff, d_out_val_off, P.oidx, n}, st);
+  if (e != hipSuccess) return hip_status(e, where);
+  hipLaunchKernelGGL(read_starts_kernel, dim3(group_blocks), dim3(256), 0, st, R);
   hipLaunchKernelGGL(merge_gather_kernel, dim3((uint32_t)((n + kMergeWaves * 64 - 1) / (kMergeWaves * 64))),
                      dim3(kMergeWaves * 64), 0, st, P);
   return hip_status(hipGetLastError(), where);

@@ -277,6 +277,14 @@ def lib():
             L.lsm_merge_runs.argtypes = [C.POINTER(LsmItems), C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        if hasattr(L, "lsm_merge_read"):  # (variant builds of earlier trees lack it: A/B scripts)
+            L.lsm_merge_read_workspace_size.restype = C.c_size_t
+            L.lsm_merge_read_workspace_size.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
+            L.lsm_merge_read.restype = C.c_int
+            L.lsm_merge_read.argtypes = [C.POINTER(LsmItems), C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64,
+                                         C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_size_t, C.c_void_p]
         if hasattr(L, "lsm_cut_blocks_device"):  # (variant builds of earlier trees lack it: A/B scripts)
             L.lsm_cut_workspace_size.restype = C.c_size_t
             L.lsm_cut_workspace_size.argtypes = [C.c_uint64]
@@ -325,7 +333,8 @@ EXPORTED_SYMBOLS = ["lsm_abi_version", "lsm_status_name", "lsm_last_error", "lsm
                     "lsm_index_entries_workspace_size", "lsm_index_entries",
                     "lsm_lz4_compress_bound", "lsm_lz4_compress_workspace_size", "lsm_lz4_compress_blocks",
                     "lsm_table_get", "lsm_table_range",
-                    "lsm_table_range_rows_workspace_size", "lsm_table_range_rows_plan", "lsm_table_range_rows"]
+                    "lsm_table_range_rows_workspace_size", "lsm_table_range_rows_plan", "lsm_table_range_rows",
+                    "lsm_merge_read_workspace_size", "lsm_merge_read"]
 
 
 def _check(rc, what):
@@ -1362,6 +1371,113 @@ def merge_runs(items, run_start, gc_seqno_threshold=0, evict_tombstones=False, z
                                 _ptr(out["n_out"]), _ptr(out["status"]), _ptr(ws), ws.numel(), _stream(stream)),
            "lsm_merge_runs")
     ws.record_stream(torch.cuda.current_stream(dev) if stream is None else stream)
+    return out
+
+
+MERGE_READ_KEEP_TOMBSTONES = 1
+
+
+def merge_read(items, run_start, n_groups, n_sources, snapshot, group_seqno=None, in_status=None,
+               keep_tombstones=False, stream=None):
+    """The snapshot read of n_groups queries over n_sources sources each (TreeIter::create_range,
+    range.rs:99-235: seqno_filter per source, Merger, MvccStream, the tombstone filter) on the
+    device.  items: device lsm_items dict, every run back to back; run_start: int64 cuda
+    [n_sources * n_groups + 1] (or a host sequence), run s * n_groups + g = source s of group g.
+    snapshot: an item is visible iff seqno < snapshot; group_seqno (int64 cuda [n_groups]) gives
+    every group its own.  in_status: int32 cuda [n_sources * n_groups], table_range_rows'
+    row_status of every run.  keep_tombstones: the kept tombstones stay in the output.
+    Returns merge_runs' dict with group_start (int64 [n_groups + 1]: group g's rows are
+    [group_start[g], group_start[g + 1])) in place of n_out, and status of [n_groups].
+    No host synchronisation."""
+    torch = _torch()
+    dev = items["keys"].device
+    if not hasattr(run_start, "data_ptr"):
+        run_start = torch.tensor(list(run_start), dtype=torch.int64, device=dev)
+    n = items["seqno"].numel()
+    it = LsmItems()
+    held = []
+    for f in ("keys", "key_off", "vals", "val_off", "seqno", "vtype"):
+        t = items[f]
+        if t.numel() == 0:  # (an empty tensor has no address; the library wants every array non-NULL)
+            t = torch.zeros(1, dtype=t.dtype, device=dev)
+            held.append(t)
+        setattr(it, f, t.data_ptr())
+    it.n_items = n
+    out = {"keys": torch.empty(items["keys"].numel() + LSM_INPUT_PADDING, dtype=torch.uint8, device=dev),
+           "vals": torch.empty(items["vals"].numel() + LSM_INPUT_PADDING, dtype=torch.uint8, device=dev),
+           "key_off": torch.empty(n + 1, dtype=torch.int64, device=dev),
+           "val_off": torch.empty(n + 1, dtype=torch.int64, device=dev),
+           "seqno": torch.empty(max(n, 1), dtype=torch.int64, device=dev),
+           "vtype": torch.empty(max(n, 1), dtype=torch.uint8, device=dev),
+           "src": torch.empty(max(n, 1), dtype=torch.int32, device=dev),
+           "group_start": torch.empty(n_groups + 1, dtype=torch.int64, device=dev),
+           "status": torch.empty(max(n_groups, 1), dtype=torch.int32, device=dev)}
+    ws = torch.empty(lib().lsm_merge_read_workspace_size(n, n_groups, n_sources), dtype=torch.uint8, device=dev)
+    flags = MERGE_READ_KEEP_TOMBSTONES if keep_tombstones else 0
+    _check(lib().lsm_merge_read(C.byref(it), _ptr(run_start), n_groups, n_sources, snapshot & (2 ** 64 - 1),
+                                _ptr(group_seqno), _ptr(in_status), flags, _ptr(out["keys"]),
+                                _ptr(out["key_off"]), _ptr(out["vals"]), _ptr(out["val_off"]), _ptr(out["seqno"]),
+                                _ptr(out["vtype"]), _ptr(out["src"]), _ptr(out["group_start"]),
+                                _ptr(out["status"]), _ptr(ws), ws.numel(), _stream(stream)), "lsm_merge_read")
+    ws.record_stream(torch.cuda.current_stream(dev) if stream is None else stream)
+    out["status"] = out["status"][:n_groups]
+    return out
+
+
+def range_read(tables, lo, lo_off, hi, hi_off, flags, snapshot, group_seqno=None, keep_tombstones=False,
+               stream=None):
+    """Tree::range(range, seqno) for a batch of ranges over several tables on the device:
+    table_range -> table_range_rows per table, each appended at the previous one's cursor, then
+    merge_read with the tables as sources (tables[0] is the lowest source: of equal (key, seqno)
+    its row comes first) and the rows calls' row_status as in_status.  tables: dicts as
+    table_range takes them, with file (padded uint8 cuda tensor), block_off (int64 cuda
+    [n_blocks + 1]) and optionally global_seqno: what write_table returns.  lo / lo_off / hi /
+    hi_off / flags: the bounds of the n ranges, as table_range.  Returns merge_read's dict
+    (n_groups = n, n_sources = len(tables)) plus row_status (int32 [len(tables) * n]).
+    One host synchronisation: the rows calls' sizes are read back to size the arenas."""
+    torch = _torch()
+    dev = flags.device
+    n, n_src = int(flags.numel()), len(tables)
+    positions, needs = [], []
+    for t in tables:
+        nb = int(t["block_off"].numel()) - 1
+        start = t.get("starts")
+        if start is None:  # (only table_range's row window reads it, which is not used here)
+            start = torch.zeros(nb + 1, dtype=torch.int32, device=dev)
+        pos = table_range(t["file"], t, lo, lo_off, hi, hi_off, flags,
+                          scan={"block_off": t["block_off"], "n_blocks": nb, "item_start": start}, stream=stream)
+        positions.append(pos)
+        # a plan with no room for rows: its need sizes the real call (pairs beyond the cap: only need[0] counts)
+        cap = min(n * nb, RANGE_ROWS_AUTO_PAIRS)
+        needs.append((cap, table_range_rows(t["file"], t, pos, t["block_off"], caps=(cap, 0, 0, 0), stream=stream,
+                                            n_queries=n)["need"]))
+    if stream is not None:
+        stream.synchronize()
+    needs = [(cap, need.cpu().tolist()) for cap, need in needs]
+    for s, (cap, need) in enumerate(needs):
+        if need[0] > cap:
+            t = tables[s]
+            again = table_range_rows(t["file"], t, positions[s], t["block_off"], caps=(need[0], 0, 0, 0),
+                                     stream=stream, n_queries=n)["need"]
+            if stream is not None:
+                stream.synchronize()
+            needs[s] = (need[0], again.cpu().tolist())
+    rows, key_bytes, val_bytes = (sum(need[k] for _, need in needs) for k in (1, 2, 3))
+    dst = _mi_alloc(dev, rows, key_bytes, val_bytes)
+    cursor, run_start, row_status = None, [], []
+    for s, t in enumerate(tables):
+        need = needs[s][1]
+        res = table_range_rows(t["file"], t, positions[s], t["block_off"], base=cursor, into=dst,
+                               caps=(need[0], need[1], key_bytes, val_bytes), stream=stream, n_queries=n)
+        cursor = res["end"]
+        run_start.append(res["run_start"][:n] if s + 1 < n_src else res["run_start"])
+        row_status.append(res["row_status"])
+    items = {"keys": dst["keys"], "key_off": dst["key_off"][:rows + 1], "vals": dst["vals"],
+             "val_off": dst["val_off"][:rows + 1], "seqno": dst["seqno"][:rows], "vtype": dst["vtype"][:rows]}
+    row_status = torch.cat(row_status)
+    out = merge_read(items, torch.cat(run_start), n, n_src, snapshot, group_seqno=group_seqno,
+                     in_status=row_status, keep_tombstones=keep_tombstones, stream=stream)
+    out["row_status"] = row_status
     return out
 
 
