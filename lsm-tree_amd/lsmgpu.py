@@ -417,7 +417,7 @@ class Decoder:
         return out
 
     def decode(self, blocks, block_off, n_blocks, out, item_cap, expect_type=-1, tuning=None, stream=None,
-               compact=False, pool=None, workspace_bytes=None):
+               compact=False, pool=None, workspace_bytes=None, blocks_bytes=None):
         """Enqueue lsm_decode_blocks (compact: lsm_decode_blocks16 into 16-bit
         offset arrays from alloc_outputs(..., compact=True)).  blocks: uint8 cuda
         (padded); block_off: int64 cuda [n+1].  pool=True: the workspace carries
@@ -425,12 +425,16 @@ class Decoder:
         workspace only (those blocks on one workgroup each); None (default): the
         pool when the batch's mean block is 32 KiB or more (its kernels cost a few
         microseconds per call even with no such block); workspace_bytes: pass
-        exactly that much workspace (tests of a pool too small for the batch)."""
+        exactly that much workspace (tests of a pool too small for the batch);
+        blocks_bytes: the batch's size where it is a small part of `blocks` (an
+        arena addressed by large offsets), default blocks.numel()."""
+        if blocks_bytes is None:
+            blocks_bytes = blocks.numel()
         if pool is None:
-            pool = blocks.numel() >= HUGE_AUTO_MEAN * max(n_blocks, 1)
+            pool = blocks_bytes >= HUGE_AUTO_MEAN * max(n_blocks, 1)
         if tuning is None and os.environ.get("LSMGPU_DECODE_TUNING"):  # diagnostic override
             tuning = tuple(int(x, 0) for x in os.environ["LSMGPU_DECODE_TUNING"].split(","))
-        ws = self.workspace(n_blocks, blocks.numel() if pool else 0)
+        ws = self.workspace(n_blocks, blocks_bytes if pool else 0)
         if workspace_bytes is not None:
             ws = _torch().empty(max(workspace_bytes, 1), dtype=_torch().uint8, device=self.device)[:workspace_bytes]
         if compact:
@@ -469,16 +473,17 @@ class Decoder:
 
 
 def decode_blocks(blocks, block_off, n_blocks=None, expect_type=-1, item_cap=None, fields=None, tuning=None,
-                  compact=False, pool=None, workspace_bytes=None):
+                  compact=False, pool=None, workspace_bytes=None, blocks_bytes=None):
     """Convenience: decode device blocks, returns dict of device tensors
-    (compact: the 19 B/item lsm_parsed_items16 layout)."""
+    (compact: the 19 B/item lsm_parsed_items16 layout).  blocks_bytes: the
+    batch's size where it is a small part of `blocks`, default blocks.numel()."""
     n_blocks = (block_off.numel() - 1) if n_blocks is None else n_blocks
     if item_cap is None:
-        item_cap = blocks.numel() // 3 + 1
+        item_cap = (blocks.numel() if blocks_bytes is None else blocks_bytes) // 3 + 1
     d = Decoder(blocks.device)
     out = d.alloc_outputs(item_cap, n_blocks, fields, compact)
     return d.decode(blocks, block_off, n_blocks, out, item_cap, expect_type, tuning, compact=compact, pool=pool,
-                    workspace_bytes=workspace_bytes)
+                    workspace_bytes=workspace_bytes, blocks_bytes=blocks_bytes)
 
 
 class Encoder:
@@ -655,13 +660,15 @@ def table_range(file, table, lo, lo_off, hi, hi_off, flags, scan=None, out=None,
     return out
 
 
-def table_block_offsets(file, table):
+def table_block_offsets(file, table, data_off=0):
     """The data-block offsets of a table (int64 cuda [n_blocks + 1], what table_range takes as
     scan["block_off"] and table_range_rows as block_off) from its block index alone, for a reader
     that never scanned the table: the TLI's entries, or, when table["two_level"], the entries of
     the partitions the TLI names, decoded as index blocks (decode_blocks, which verifies them).
     table as table_range takes it.  Raises LsmError when an index block does not decode or the
-    handles are not contiguous from 0 (the layout a scan reads back to back).  Synchronises."""
+    handles are not contiguous from data_off (default 0: the layout a scan reads back to back; a
+    table laid further into a larger image gives the offset of its first data block).
+    Synchronises."""
     import numpy as np
     torch = _torch()
     dev = file.device
@@ -680,7 +687,7 @@ def table_block_offsets(file, table):
             off = torch.tensor([h[0] for h in run] + [run[-1][0] + run[-1][1]], dtype=torch.int64, device=dev)
             cap = sum(size for _, size in run) // 5 + len(run)  # (an index record takes 5 bytes or more)
             d = decode_blocks(file, off, len(run), expect_type=BLOCK_INDEX, item_cap=cap,
-                              fields=["handle_off", "val_len"])
+                              fields=["handle_off", "val_len"], blocks_bytes=sum(size for _, size in run))
             status = d["status"][:len(run)].cpu().numpy()
             if status.any():
                 raise LsmError(f"table_block_offsets: index block status {STATUS.get(int(status.max()), '?')}")
@@ -692,10 +699,10 @@ def table_block_offsets(file, table):
     handles = entries([(table["tli_off"], table["tli_size"])])
     if table.get("two_level", False):
         handles = entries(handles)
-    off = np.zeros(len(handles) + 1, np.int64)
+    off = np.full(len(handles) + 1, data_off, np.int64)
     for i, (o, size) in enumerate(handles):
         if o != off[i]:
-            raise LsmError(f"table_block_offsets: data block {i} at {o}, not contiguous from 0")
+            raise LsmError(f"table_block_offsets: data block {i} at {o}, not contiguous from {data_off}")
         off[i + 1] = o + size
     if off[-1] > file_len:
         raise LsmError("table_block_offsets: the data blocks end past the file")
@@ -1065,18 +1072,21 @@ def decode_lz4_blocks(blocks, block_off, n_blocks=None, expect_type=-1, item_cap
     return out
 
 
-def lz4_compress_blocks(blocks, block_off, n_blocks=None, in_status=None, out_cap=None, stream=None):
+def lz4_compress_blocks(blocks, block_off, n_blocks=None, in_status=None, out_cap=None, stream=None,
+                        blocks_bytes=None):
     """Block::write_into with CompressionType::Lz4 over a batch (block/mod.rs:60-74):
     blocks = padded uint8 cuda tensor of uncompressed blocks as Encoder.encode wrote them,
     block_off = int64 cuda [n+1], in_status = the encoder's status (or None).  Each block
     becomes Header' || LZ4 stream of its payload, packed from offset 0.  out_cap defaults to
-    lsm_lz4_compress_bound of the input buffer, which cannot overflow.  No host
+    lsm_lz4_compress_bound of the input buffer (of blocks_bytes, where the batch is a small
+    part of `blocks`), which cannot overflow.  No host
     synchronisation.  Returns dict(buf: uint8 cuda, padded by LSM_INPUT_PADDING so it feeds
     decode_lz4_blocks; block_off: int64 cuda [n+1]; status: int32 cuda [n])."""
     torch = _torch()
     n = block_off.numel() - 1 if n_blocks is None else n_blocks
     dev = blocks.device
-    blocks_bytes = blocks.numel()  # (an upper bound of block_off[n] - block_off[0]: no read-back)
+    if blocks_bytes is None:
+        blocks_bytes = blocks.numel()  # (an upper bound of block_off[n] - block_off[0]: no read-back)
     if out_cap is None:
         out_cap = int(lib().lsm_lz4_compress_bound(blocks_bytes, n))
     buf = padded_bytes(out_cap, dev)
