@@ -3,11 +3,20 @@
 Device memory comes from torch CUDA tensors (plumbing only).  Every call goes
 through the C ABI; there is no CPU fallback: importing this module on a box
 without the built library raises, and calls without a GPU fail loudly.
+
+The functions' signatures are not written down here: lib() types every entry
+point from its prototype in include/lsmgpu.h (EXPORTED_SYMBOLS: their names in
+header order), so a new entry point is declared in the header and listed in
+exports.map, nowhere else.  Only the structs are mirrored (the Lsm* classes;
+tests/test_abi.py holds them to the header).  Every wrapper takes its
+temporary workspace from _workspace and reads device values back through
+_read_back, which keep both sound on a caller's side stream.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 from pathlib import Path
 
 HERE = Path(__file__).resolve().parent
@@ -102,239 +111,62 @@ def build():
 _lib = None
 
 
+_C_SCALARS = {"int": C.c_int, "size_t": C.c_size_t, "float": C.c_float,
+              **{f"{u}int{b}_t": getattr(C, f"c_{u}int{b}") for u in ("", "u") for b in (8, 16, 32, 64)}}
+_C_STRUCTS = {"lsm_items": LsmItems, "lsm_items32": LsmItems32, "lsm_parsed_items": LsmParsed,
+              "lsm_parsed_items16": LsmParsed16, "lsm_block_params": LsmBlockParams,
+              "lsm_point_result": LsmPointResult, "lsm_decode_tuning": LsmDecodeTuning,
+              "lsm_table_scan": LsmTableScan, "lsm_range_result": LsmRangeResult,
+              "lsm_range_positions": LsmRangePositions}
+
+
+def _prototypes():
+    """{name: (return type, [parameter types])} of every function include/lsmgpu.h declares, as C
+    type strings, in header order."""
+    text = re.sub(r"/\*.*?\*/", "", (HERE.parent / "include" / "lsmgpu.h").read_text(), flags=re.S)
+    protos = {}
+    for ret, name, params in re.findall(r"^(\w[\w \*]*?)\s*\b(lsm_\w+)\s*\(([^()]*)\)\s*;", text, re.M):
+        params = [] if params.strip() == "void" else params.split(",")
+        protos[name] = (ret, [re.sub(r"\w+\s*$", "", p) for p in params])  # (the type: all but the name)
+    return protos
+
+
+PROTOTYPES = _prototypes()
+EXPORTED_SYMBOLS = list(PROTOTYPES)
+
+
+def _c_type(name, ctype, ret=False):
+    """The ctypes type of one parameter (ret: of the return value) of prototype `name`: a scalar,
+    POINTER(the mirrored Structure), c_char_p for a returned const char*, c_void_p for every other
+    pointer to a known type.  Anything else is an LsmError: the binding does not guess."""
+    m = re.fullmatch(r"\s*(?:const\s+)?(\w+)\s*(\*?)\s*", ctype)
+    base, ptr = m.groups() if m else (None, None)
+    if base in _C_SCALARS and not ptr:
+        return _C_SCALARS[base]
+    if base in _C_STRUCTS and ptr:
+        return C.POINTER(_C_STRUCTS[base])
+    if base == "char" and ptr and ret:
+        return C.c_char_p
+    if (base == "void" or base in _C_SCALARS) and ptr:
+        return C.c_void_p
+    raise LsmError(f"{name}: no ctypes mapping for the C type {ctype.strip()!r} in include/lsmgpu.h")
+
+
 def lib():
+    """The loaded library, every function the header declares typed from its prototype.  A symbol
+    the library lacks is skipped: LSMGPU_LIB may name a variant built from an earlier tree."""
     global _lib
     if _lib is None:
         if not LIB_PATH.exists():
             raise LsmError(f"{LIB_PATH} not built: run `make -C {HERE}` (or __graft_entry__.build())")
         L = C.CDLL(str(LIB_PATH))
-        L.lsm_abi_version.restype = C.c_int
-        L.lsm_status_name.restype = C.c_char_p
-        L.lsm_status_name.argtypes = [C.c_int]
-        L.lsm_last_error.restype = C.c_char_p
-        L.lsm_device_count.restype = C.c_int
-        L.lsm_set_device.restype = C.c_int
-        L.lsm_set_device.argtypes = [C.c_int]
-        L.lsm_decode_workspace_size.restype = C.c_size_t
-        L.lsm_decode_workspace_size.argtypes = [C.c_uint32]
-        L.lsm_decode_workspace_size_ex.restype = C.c_size_t
-        L.lsm_decode_workspace_size_ex.argtypes = [C.c_uint32, C.c_uint64]
-        L.lsm_decode_blocks.restype = C.c_int
-        L.lsm_decode_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(LsmParsed),
-                                        C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.lsm_decode_blocks_tuned.restype = C.c_int
-        L.lsm_decode_blocks_tuned.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(LsmParsed),
-                                              C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                              C.POINTER(LsmDecodeTuning), C.c_void_p]
-        L.lsm_decode_blocks16.restype = C.c_int
-        L.lsm_decode_blocks16.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(LsmParsed16),
-                                          C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                          C.POINTER(LsmDecodeTuning), C.c_void_p]
-        L.lsm_encode_bound.restype = C.c_uint64
-        L.lsm_encode_bound.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(LsmBlockParams)]
-        L.lsm_encode_workspace_size.restype = C.c_size_t
-        L.lsm_encode_workspace_size.argtypes = [C.c_uint64, C.c_uint32]
-        L.lsm_encode_workspace_size_ex.restype = C.c_size_t
-        L.lsm_encode_workspace_size_ex.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64]
-        L.lsm_encode_blocks.restype = C.c_int
-        L.lsm_encode_blocks.argtypes = [C.POINTER(LsmItems), C.c_void_p, C.c_uint32, C.POINTER(LsmBlockParams),
-                                        C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                        C.c_void_p]
-        if hasattr(L, "lsm_encode_blocks32"):  # (variant builds of earlier trees lack it: A/B scripts)
-            L.lsm_encode_blocks32.restype = C.c_int
-            L.lsm_encode_blocks32.argtypes = [C.POINTER(LsmItems32), C.c_void_p, C.c_uint32,
-                                              C.POINTER(LsmBlockParams), C.c_void_p, C.c_uint64, C.c_void_p,
-                                              C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.lsm_cut_blocks.restype = C.c_uint64
-        L.lsm_cut_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64]
-        L.lsm_xxh3_128_batch.restype = C.c_int
-        L.lsm_xxh3_128_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
-        L.lsm_xxh3_128_file_workspace_size.restype = C.c_size_t
-        L.lsm_xxh3_128_file_workspace_size.argtypes = [C.c_uint64]
-        L.lsm_xxh3_128_file.restype = C.c_int
-        L.lsm_xxh3_128_file.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.lsm_xxh3_128_stream_state_size.restype = C.c_size_t
-        L.lsm_xxh3_128_stream_state_size.argtypes = []
-        L.lsm_xxh3_128_stream_workspace_size.restype = C.c_size_t
-        L.lsm_xxh3_128_stream_workspace_size.argtypes = [C.c_uint64]
-        L.lsm_xxh3_128_stream_init.restype = C.c_int
-        L.lsm_xxh3_128_stream_init.argtypes = [C.c_void_p, C.c_void_p]
-        L.lsm_xxh3_128_stream_update.restype = C.c_int
-        L.lsm_xxh3_128_stream_update.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t,
-                                                 C.c_void_p]
-        L.lsm_xxh3_128_stream_digest.restype = C.c_int
-        L.lsm_xxh3_128_stream_digest.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.lsm_xxh3_128_stream_init_batch.restype = C.c_int
-        L.lsm_xxh3_128_stream_init_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
-        L.lsm_xxh3_128_stream_batch_workspace_size.restype = C.c_size_t
-        L.lsm_xxh3_128_stream_batch_workspace_size.argtypes = [C.c_uint32, C.c_uint64]
-        L.lsm_xxh3_128_stream_update_batch.restype = C.c_int
-        L.lsm_xxh3_128_stream_update_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
-                                                       C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.lsm_xxh3_128_stream_digest_batch.restype = C.c_int
-        L.lsm_xxh3_128_stream_digest_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
-        L.lsm_point_read_blocks.restype = C.c_int
-        L.lsm_point_read_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_uint32, C.POINTER(LsmPointResult), C.c_void_p,
-                                            C.c_void_p]
-        L.lsm_seek_blocks.restype = C.c_int
-        L.lsm_seek_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_void_p, C.c_void_p]
-        L.lsm_bloom_calculate_m.restype = C.c_uint64
-        L.lsm_bloom_calculate_m.argtypes = [C.c_uint64, C.c_float]
-        L.lsm_bloom_shape.restype = C.c_int
-        L.lsm_bloom_shape.argtypes = [C.c_uint64, C.c_int, C.c_float, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-        L.lsm_bloom_filter_size.restype = C.c_uint64
-        L.lsm_bloom_filter_size.argtypes = [C.c_uint64]
-        L.lsm_hash64_keys.restype = C.c_int
-        L.lsm_hash64_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-        L.lsm_bloom_build.restype = C.c_int
-        L.lsm_bloom_build.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64,
-                                      C.c_void_p]
-        L.lsm_bloom_contains.restype = C.c_int
-        L.lsm_bloom_contains.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-        L.lsm_lz4_workspace_size.restype = C.c_size_t
-        L.lsm_lz4_workspace_size.argtypes = [C.c_uint32]
-        L.lsm_lz4_decompress_blocks.restype = C.c_int
-        L.lsm_lz4_decompress_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
-                                                C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.lsm_lz4_plan_workspace_size.restype = C.c_size_t
-        L.lsm_lz4_plan_workspace_size.argtypes = [C.c_uint32]
-        L.lsm_lz4_plan_output.restype = C.c_int
-        L.lsm_lz4_plan_output.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p,
-                                          C.c_size_t, C.c_void_p]
-        for fn in (L.lsm_lz4_plan_framed,):
-            fn.restype = C.c_int
-            fn.argtypes = L.lsm_lz4_plan_output.argtypes
-        L.lsm_lz4_decompress_framed.restype = C.c_int
-        L.lsm_lz4_decompress_framed.argtypes = L.lsm_lz4_decompress_blocks.argtypes
-        L.lsm_scan_workspace_size.restype = C.c_size_t
-        L.lsm_scan_workspace_size.argtypes = [C.c_uint32]
-        L.lsm_scan_table_async.restype = C.c_int
-        L.lsm_scan_table_async.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(LsmTableScan), C.c_void_p, C.c_uint32,
-                                           C.c_uint32, C.c_uint32, C.POINTER(LsmParsed), C.c_uint64, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.lsm_scan_table.restype = C.c_int
-        L.lsm_scan_table.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(LsmTableScan), C.c_void_p, C.c_uint32,
-                                     C.POINTER(LsmParsed), C.c_uint64, C.c_void_p, C.c_void_p,
-                                     C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.c_void_p, C.c_size_t, C.c_void_p]
-        if hasattr(L, "lsm_table_get"):  # (variant builds of earlier trees lack it: A/B scripts)
-            L.lsm_table_get.restype = C.c_int
-            L.lsm_table_get.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(LsmTableScan), C.c_uint64, C.c_uint32,
-                                        C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_uint32, C.POINTER(LsmPointResult), C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p]
-        if hasattr(L, "lsm_table_range"):  # (variant builds of earlier trees lack it: A/B scripts)
-            L.lsm_table_range.restype = C.c_int
-            L.lsm_table_range.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(LsmTableScan), C.c_void_p, C.c_void_p,
-                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
-                                          C.POINTER(LsmRangeResult), C.c_void_p, C.c_void_p, C.c_void_p]
-        if hasattr(L, "lsm_table_range_rows"):  # (variant builds of earlier trees lack it: A/B scripts)
-            L.lsm_table_range_rows_workspace_size.restype = C.c_size_t
-            L.lsm_table_range_rows_workspace_size.argtypes = [C.c_uint32, C.c_uint64, C.c_uint64]
-            rr_inputs = [C.c_void_p, C.c_uint64, C.POINTER(LsmTableScan), C.c_void_p, C.c_uint32,
-                         C.POINTER(LsmRangePositions), C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]  # .. d_base
-            L.lsm_table_range_rows_plan.restype = C.c_int
-            L.lsm_table_range_rows_plan.argtypes = rr_inputs + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                                C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-            L.lsm_table_range_rows.restype = C.c_int
-            L.lsm_table_range_rows.argtypes = rr_inputs + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
-                                                           C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
-                                                           C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-        L.lsm_materialize_workspace_size.restype = C.c_size_t
-        L.lsm_materialize_workspace_size.argtypes = [C.c_uint64]
-        L.lsm_materialize_plan.restype = C.c_int
-        L.lsm_materialize_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
-                                           C.POINTER(LsmParsed), C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t,
-                                           C.c_void_p]
-        L.lsm_materialize_keys_capped.restype = C.c_int
-        L.lsm_materialize_keys_capped.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
-                                                  C.POINTER(LsmParsed), C.c_uint64, C.c_void_p, C.c_void_p,
-                                                  C.c_uint64, C.c_void_p, C.c_void_p]
-        L.lsm_lz4_plan_capped.restype = C.c_int
-        L.lsm_lz4_plan_capped.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_uint64,
-                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.lsm_materialize_keys.restype = C.c_int
-        L.lsm_materialize_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
-                                           C.POINTER(LsmParsed), C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
-        if hasattr(L, "lsm_materialize_items"):  # (variant builds of earlier trees lack it: A/B scripts)
-            L.lsm_materialize_items_workspace_size.restype = C.c_size_t
-            L.lsm_materialize_items_workspace_size.argtypes = [C.c_uint64]
-            mi_inputs = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
-                         C.POINTER(LsmParsed), C.c_uint64, C.c_void_p]  # d_blocks .. d_base
-            L.lsm_materialize_items_plan.restype = C.c_int
-            L.lsm_materialize_items_plan.argtypes = mi_inputs + [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
-                                                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-            L.lsm_materialize_items.restype = C.c_int
-            L.lsm_materialize_items.argtypes = mi_inputs + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                            C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
-                                                            C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-        if hasattr(L, "lsm_merge_runs"):  # (variant builds of earlier trees lack it: A/B scripts)
-            L.lsm_merge_workspace_size.restype = C.c_size_t
-            L.lsm_merge_workspace_size.argtypes = [C.c_uint64, C.c_uint32]
-            L.lsm_merge_runs.restype = C.c_int
-            L.lsm_merge_runs.argtypes = [C.POINTER(LsmItems), C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        if hasattr(L, "lsm_merge_read"):  # (variant builds of earlier trees lack it: A/B scripts)
-            L.lsm_merge_read_workspace_size.restype = C.c_size_t
-            L.lsm_merge_read_workspace_size.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
-            L.lsm_merge_read.restype = C.c_int
-            L.lsm_merge_read.argtypes = [C.POINTER(LsmItems), C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64,
-                                         C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_size_t, C.c_void_p]
-        if hasattr(L, "lsm_cut_blocks_device"):  # (variant builds of earlier trees lack it: A/B scripts)
-            L.lsm_cut_workspace_size.restype = C.c_size_t
-            L.lsm_cut_workspace_size.argtypes = [C.c_uint64]
-            L.lsm_cut_blocks_device.restype = C.c_int
-            L.lsm_cut_blocks_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
-                                                C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
-                                                C.c_void_p, C.c_size_t, C.c_void_p]
-            L.lsm_index_entries_workspace_size.restype = C.c_size_t
-            L.lsm_index_entries_workspace_size.argtypes = [C.c_uint32]
-            L.lsm_index_entries.restype = C.c_int
-            L.lsm_index_entries.argtypes = [C.POINTER(LsmItems), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64,
-                                            C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        if hasattr(L, "lsm_lz4_compress_blocks"):  # (variant builds of earlier trees lack it: A/B scripts)
-            L.lsm_lz4_compress_bound.restype = C.c_uint64
-            L.lsm_lz4_compress_bound.argtypes = [C.c_uint64, C.c_uint32]
-            L.lsm_lz4_compress_workspace_size.restype = C.c_size_t
-            L.lsm_lz4_compress_workspace_size.argtypes = [C.c_uint32, C.c_uint64]
-            L.lsm_lz4_compress_blocks.restype = C.c_int
-            L.lsm_lz4_compress_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
-                                                  C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                                  C.c_void_p]
+        for name, (ret, params) in PROTOTYPES.items():
+            if hasattr(L, name):
+                fn = getattr(L, name)
+                fn.restype = _c_type(name, ret, ret=True)
+                fn.argtypes = [_c_type(name, p) for p in params]
         _lib = L
     return _lib
-
-
-EXPORTED_SYMBOLS = ["lsm_abi_version", "lsm_status_name", "lsm_last_error", "lsm_device_count", "lsm_set_device",
-                    "lsm_decode_workspace_size", "lsm_decode_workspace_size_ex", "lsm_decode_blocks", "lsm_decode_blocks_tuned", "lsm_decode_blocks16",
-                    "lsm_encode_bound",
-                    "lsm_encode_workspace_size", "lsm_encode_workspace_size_ex", "lsm_encode_blocks", "lsm_encode_blocks32",
-                    "lsm_cut_blocks", "lsm_xxh3_128_batch",
-                    "lsm_point_read_blocks", "lsm_xxh3_128_file_workspace_size", "lsm_xxh3_128_file",
-                    "lsm_bloom_calculate_m", "lsm_bloom_shape", "lsm_bloom_filter_size", "lsm_hash64_keys",
-                    "lsm_bloom_build", "lsm_bloom_contains", "lsm_lz4_workspace_size", "lsm_lz4_decompress_blocks",
-                    "lsm_lz4_plan_workspace_size", "lsm_lz4_plan_output", "lsm_seek_blocks", "lsm_lz4_plan_framed",
-                    "lsm_lz4_decompress_framed", "lsm_scan_workspace_size", "lsm_scan_table", "lsm_scan_table_async",
-                    "lsm_materialize_workspace_size", "lsm_materialize_plan", "lsm_materialize_keys",
-                    "lsm_materialize_keys_capped", "lsm_lz4_plan_capped",
-                    "lsm_materialize_items_workspace_size", "lsm_materialize_items_plan", "lsm_materialize_items",
-                    "lsm_xxh3_128_stream_state_size", "lsm_xxh3_128_stream_workspace_size",
-                    "lsm_xxh3_128_stream_init", "lsm_xxh3_128_stream_update", "lsm_xxh3_128_stream_digest",
-                    "lsm_xxh3_128_stream_init_batch", "lsm_xxh3_128_stream_batch_workspace_size",
-                    "lsm_xxh3_128_stream_update_batch", "lsm_xxh3_128_stream_digest_batch",
-                    "lsm_merge_workspace_size", "lsm_merge_runs",
-                    "lsm_cut_workspace_size", "lsm_cut_blocks_device",
-                    "lsm_index_entries_workspace_size", "lsm_index_entries",
-                    "lsm_lz4_compress_bound", "lsm_lz4_compress_workspace_size", "lsm_lz4_compress_blocks",
-                    "lsm_table_get", "lsm_table_range",
-                    "lsm_table_range_rows_workspace_size", "lsm_table_range_rows_plan", "lsm_table_range_rows",
-                    "lsm_merge_read_workspace_size", "lsm_merge_read"]
 
 
 def _check(rc, what):
@@ -357,6 +189,68 @@ def _stream(stream):
 
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _workspace(nbytes, device, stream=None):
+    """A call's temporary workspace: uint8 [nbytes] on `device`, recorded on the stream the call
+    launches on (`stream`, else the device's current one), so that the caching allocator hands
+    the bytes on only to work queued after the kernels that use them."""
+    torch = _torch()
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    if ws.is_cuda:
+        ws.record_stream(stream if stream is not None else torch.cuda.current_stream(ws.device))
+    return ws
+
+
+def _read_back(t, stream=None):
+    """A device tensor's values on the host (tolist()), read after the work queued on `stream`:
+    the copy runs on the current stream, which does not wait for a side stream by itself."""
+    if stream is not None:
+        stream.synchronize()
+    return t.cpu().tolist()
+
+
+ITEM_FIELDS = ("keys", "key_off", "vals", "val_off", "seqno", "vtype")
+
+
+def _items_struct(items, fields=ITEM_FIELDS, cls=LsmItems):
+    """The lsm_items (cls: LsmItems or LsmItems32) over those of `fields` an items dict holds, the
+    others NULL, n_items from seqno.  Returns (struct, held): an empty tensor has no address and
+    the library wants its arrays non-NULL, so one element stands in, kept alive by `held`."""
+    it, held = cls(n_items=items["seqno"].numel()), []
+    for f in fields:
+        t = items.get(f)
+        if t is not None and t.numel() == 0:
+            t = t.new_zeros(1)
+            held.append(t)
+        setattr(it, f, t.data_ptr() if t is not None else None)
+    return it, held
+
+
+def _items_view(dst, rows=None):
+    """The six lsm_items tensors of dst; rows: the per-row arrays trimmed to that many rows."""
+    items = {f: dst[f] for f in ITEM_FIELDS}
+    if rows is not None:
+        items.update(key_off=dst["key_off"][:rows + 1], val_off=dst["val_off"][:rows + 1],
+                     seqno=dst["seqno"][:rows], vtype=dst["vtype"][:rows])
+    return items
+
+
+def _parsed_struct(out, cls=LsmParsed):
+    """The lsm_parsed_items (cls=LsmParsed16: lsm_parsed_items16) over a decode output dict; fields
+    it does not hold are NULL (not written)."""
+    return cls(*(_ptr(out.get(f)) for f, _ in cls._fields_))
+
+
+def _table_struct(table, global_seqno=0, block_count=0):
+    """The lsm_table_scan of a table dict (tli_off, tli_size, optionally two_level)."""
+    return LsmTableScan(table["tli_off"], table["tli_size"], int(bool(table.get("two_level", False))),
+                        global_seqno & (2 ** 64 - 1), block_count)
+
+
+def _file_len(table, other_end=0):
+    """table["file_len"], else the end of the TLI (or of another region that ends later)."""
+    return table.get("file_len", max(table["tli_off"] + table["tli_size"], other_end))
 
 
 def padded_bytes(n, device="cuda"):
@@ -436,38 +330,27 @@ class Decoder:
             tuning = tuple(int(x, 0) for x in os.environ["LSMGPU_DECODE_TUNING"].split(","))
         ws = self.workspace(n_blocks, blocks_bytes if pool else 0)
         if workspace_bytes is not None:
-            ws = _torch().empty(max(workspace_bytes, 1), dtype=_torch().uint8, device=self.device)[:workspace_bytes]
+            ws = _workspace(max(workspace_bytes, 1), self.device, stream)[:workspace_bytes]
+        if pool:  # the pool is an explicit opt-in (LSM_DECODE_HUGE_POOL), never implied by the size
+            tuning = tuple(tuning or (0, 0, 0))
+            tuning = tuning[:3] + ((tuning[3] if len(tuning) > 3 else 0) | DECODE_HUGE_POOL,)
+        # (blocks_per_wave, stage_bytes, tile_items[, flags])
+        t = C.byref(LsmDecodeTuning(*tuning)) if tuning is not None else None
+        args = (_ptr(blocks), _ptr(block_off), n_blocks, expect_type)
+        tail = (item_cap, _ptr(out["item_start"]), _ptr(out["status"]), _ptr(ws), ws.numel())
         if compact:
-            ps = LsmParsed16()
             for f, dt in PARSED16_FIELDS:
                 if f in out and out[f].element_size() != C.sizeof(C.c_uint64 if dt == "int64" else
                                                                   C.c_uint16 if dt == "int16" else C.c_uint8):
                     raise LsmError(f"compact decode: field {f} must be {dt}")
-                setattr(ps, f, out[f].data_ptr() if f in out else None)
-            if pool:
-                tuning = tuple(tuning or (0, 0, 0))
-                tuning = tuning[:3] + ((tuning[3] if len(tuning) > 3 else 0) | DECODE_HUGE_POOL,)
-            t = C.byref(LsmDecodeTuning(*tuning)) if tuning is not None else None
-            rc = lib().lsm_decode_blocks16(_ptr(blocks), _ptr(block_off), n_blocks, expect_type, C.byref(ps),
-                                           item_cap, _ptr(out["item_start"]), _ptr(out["status"]), _ptr(ws),
-                                           ws.numel(), t, _stream(stream))
-            _check(rc, "lsm_decode_blocks16")
+            ps = _parsed_struct(out, LsmParsed16)
+            _check(lib().lsm_decode_blocks16(*args, C.byref(ps), *tail, t, _stream(stream)), "lsm_decode_blocks16")
             return out
-        ps = LsmParsed()
-        for f, _ in PARSED_FIELDS:
-            setattr(ps, f, out[f].data_ptr() if f in out else None)
-        if pool:  # the pool is an explicit opt-in (LSM_DECODE_HUGE_POOL), never implied by the size
-            tuning = tuple(tuning or (0, 0, 0))
-            tuning = tuning[:3] + ((tuning[3] if len(tuning) > 3 else 0) | DECODE_HUGE_POOL,)
-        if tuning is not None:
-            t = LsmDecodeTuning(*tuning)  # (blocks_per_wave, stage_bytes, tile_items[, flags])
-            rc = lib().lsm_decode_blocks_tuned(_ptr(blocks), _ptr(block_off), n_blocks, expect_type, C.byref(ps),
-                                               item_cap, _ptr(out["item_start"]), _ptr(out["status"]), _ptr(ws),
-                                               ws.numel(), C.byref(t), _stream(stream))
+        ps = _parsed_struct(out)
+        if t is not None:
+            rc = lib().lsm_decode_blocks_tuned(*args, C.byref(ps), *tail, t, _stream(stream))
         else:
-            rc = lib().lsm_decode_blocks(_ptr(blocks), _ptr(block_off), n_blocks, expect_type, C.byref(ps), item_cap,
-                                         _ptr(out["item_start"]), _ptr(out["status"]), _ptr(ws), ws.numel(),
-                                         _stream(stream))
+            rc = lib().lsm_decode_blocks(*args, C.byref(ps), *tail, _stream(stream))
         _check(rc, "lsm_decode_blocks")
         return out
 
@@ -504,16 +387,9 @@ class Encoder:
         off32 = items["key_off"].element_size() == 4
         if off32 and "val_off" in items and items["val_off"].element_size() != 4:
             raise LsmError("key_off and val_off must have the same width")
-        it = LsmItems32() if off32 else LsmItems()
-        it.keys = items["keys"].data_ptr()
-        it.key_off = items["key_off"].data_ptr()
-        it.vals = items["vals"].data_ptr() if "vals" in items else items["keys"].data_ptr()
-        it.val_off = items["val_off"].data_ptr() if "val_off" in items else items["key_off"].data_ptr()
-        it.seqno = items["seqno"].data_ptr()
-        it.vtype = items["vtype"].data_ptr() if "vtype" in items else None
-        it.handle_off = items["handle_off"].data_ptr() if "handle_off" in items else None
-        it.handle_size = items["handle_size"].data_ptr() if "handle_size" in items else None
-        it.n_items = n_items
+        # (index-form items carry no values: the value fields then alias the keys)
+        it, held = _items_struct({"vals": items["keys"], "val_off": items["key_off"], **items},
+                                 ITEM_FIELDS + ("handle_off", "handle_size"), LsmItems32 if off32 else LsmItems)
         params = LsmBlockParams(restart_interval, block_type, 0, 0, hash_ratio, 0)
         key_bytes = int(items["keys"].numel())
         val_bytes = int(items["vals"].numel()) if "vals" in items else 0
@@ -598,13 +474,11 @@ def table_get(file, table, needles, needle_off, snapshot, key_hash=None, active=
     if out is None:
         out = {f: torch.zeros(max(n, 1), dtype=getattr(torch, dt), device=dev) for f, dt in TABLE_GET_FIELDS}
     f_off, f_size = filter if filter is not None else (0, 0)
-    file_len = table.get("file_len", max(table["tli_off"] + table["tli_size"], f_off + f_size))
-    t = LsmTableScan(table["tli_off"], table["tli_size"], int(bool(table.get("two_level", False))),
-                     global_seqno & (2 ** 64 - 1), 0)
+    t = _table_struct(table, global_seqno)
     res = _point_result(out)
-    _check(lib().lsm_table_get(_ptr(file), file_len, C.byref(t), f_off, f_size, lowest_seqno, _ptr(needles),
-                               _ptr(needle_off), _ptr(snapshot), _ptr(key_hash), _ptr(active), n, C.byref(res),
-                               _ptr(out["block_off"]), _ptr(out["block_size"]), _ptr(out["outcome"]),
+    _check(lib().lsm_table_get(_ptr(file), _file_len(table, f_off + f_size), C.byref(t), f_off, f_size, lowest_seqno,
+                               _ptr(needles), _ptr(needle_off), _ptr(snapshot), _ptr(key_hash), _ptr(active), n,
+                               C.byref(res), _ptr(out["block_off"]), _ptr(out["block_size"]), _ptr(out["outcome"]),
                                _ptr(out["status"]), _stream(stream)), "lsm_table_get")
     return out
 
@@ -636,8 +510,7 @@ def table_range(file, table, lo, lo_off, hi, hi_off, flags, scan=None, out=None,
     dev = file.device
     if out is None:
         out = {f: torch.zeros(max(n, 1), dtype=getattr(torch, dt), device=dev) for f, dt in TABLE_RANGE_FIELDS}
-    file_len = table.get("file_len", table["tli_off"] + table["tli_size"])
-    t = LsmTableScan(table["tli_off"], table["tli_size"], int(bool(table.get("two_level", False))), 0, 0)
+    t = _table_struct(table)
     block_off, n_blocks = None, 0
     if scan is not None:
         block_off = scan["block_off"]
@@ -645,9 +518,9 @@ def table_range(file, table, lo, lo_off, hi, hi_off, flags, scan=None, out=None,
         n_blocks = nb if isinstance(nb, int) else int(block_off.numel()) - 1
     res = LsmRangeResult(*(_ptr(out[f]) if block_off is not None or not f.endswith("_block") else None
                            for f, _ in TABLE_RANGE_FIELDS[:8]))
-    _check(lib().lsm_table_range(_ptr(file), file_len, C.byref(t), _ptr(lo), _ptr(lo_off), _ptr(hi), _ptr(hi_off),
-                                 _ptr(flags), n, _ptr(block_off), n_blocks, C.byref(res), _ptr(out["outcome"]),
-                                 _ptr(out["status"]), _stream(stream)), "lsm_table_range")
+    _check(lib().lsm_table_range(_ptr(file), _file_len(table), C.byref(t), _ptr(lo), _ptr(lo_off), _ptr(hi),
+                                 _ptr(hi_off), _ptr(flags), n, _ptr(block_off), n_blocks, C.byref(res),
+                                 _ptr(out["outcome"]), _ptr(out["status"]), _stream(stream)), "lsm_table_range")
     if scan is not None:
         rows = out["outcome"][:n] == RANGE_ROWS
         start = scan["item_start"].to(torch.int64)
@@ -672,7 +545,7 @@ def table_block_offsets(file, table, data_off=0):
     import numpy as np
     torch = _torch()
     dev = file.device
-    file_len = table.get("file_len", table["tli_off"] + table["tli_size"])
+    file_len = _file_len(table)
 
     def entries(handles):
         """[(off, size)] of index blocks -> the handles their entries hold, in order."""
@@ -738,15 +611,12 @@ def table_range_rows(file, table, positions, block_off, base=None, into=None, ca
     dev = file.device
     n = int(positions["outcome"].numel()) if n_queries is None else int(n_queries)
     n_blocks = int(block_off.numel()) - 1
-    file_len = table.get("file_len", table["tli_off"] + table["tli_size"])
-    t = LsmTableScan(table["tli_off"], table["tli_size"], int(bool(table.get("two_level", False))),
-                     table.get("global_seqno", 0) & (2 ** 64 - 1), 0)
-    ps = LsmRangePositions(*(_ptr(positions[f]) for f in ("outcome", "status", "first_block", "first_item",
-                                                          "last_block", "last_item")))
+    t = _table_struct(table, table.get("global_seqno", 0))
+    ps = LsmRangePositions(*(_ptr(positions[f]) for f, _ in LsmRangePositions._fields_))
     if base is not None and into is None:
         raise LsmError("table_range_rows: a base needs `into` (the outputs it already fills)")
     st = _stream(stream)
-    cur = torch.cuda.current_stream(dev) if stream is None else stream
+    head = (_ptr(file), _file_len(table), C.byref(t), _ptr(block_off), n_blocks, C.byref(ps), n)  # both calls'
     run_start = torch.zeros(n + 1, dtype=torch.int64, device=dev)
     row_status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
     end = torch.zeros(3, dtype=torch.int64, device=dev)
@@ -755,19 +625,11 @@ def table_range_rows(file, table, positions, block_off, base=None, into=None, ca
     plan_result = torch.zeros(1, dtype=torch.int32, device=dev)
 
     def plan(block_cap, row_cap):
-        ws = torch.empty(lib().lsm_table_range_rows_workspace_size(n, block_cap, row_cap), dtype=torch.uint8,
-                         device=dev)
-        _check(lib().lsm_table_range_rows_plan(_ptr(file), file_len, C.byref(t), _ptr(block_off), n_blocks,
-                                               C.byref(ps), n, block_cap, row_cap, _ptr(base), _ptr(run_start),
-                                               _ptr(end), _ptr(need), _ptr(row_status), _ptr(plan_result), _ptr(ws),
+        ws = _workspace(lib().lsm_table_range_rows_workspace_size(n, block_cap, row_cap), dev, stream)
+        _check(lib().lsm_table_range_rows_plan(*head, block_cap, row_cap, _ptr(base), _ptr(run_start), _ptr(end),
+                                               _ptr(need), _ptr(row_status), _ptr(plan_result), _ptr(ws),
                                                ws.numel(), st), "lsm_table_range_rows_plan")
-        ws.record_stream(cur)
         return ws
-
-    def read_need():
-        if stream is not None:
-            stream.synchronize()
-        return need.cpu().tolist()
 
     trim = None
     explicit = caps is not None
@@ -775,9 +637,9 @@ def table_range_rows(file, table, positions, block_off, base=None, into=None, ca
         bound = n * n_blocks
         if bound > RANGE_ROWS_AUTO_PAIRS:
             plan(0, 0)
-            bound = read_need()[0]
+            bound = _read_back(need, stream)[0]
         plan(bound, 0)
-        pairs, rows, key_bytes, val_bytes = read_need()
+        pairs, rows, key_bytes, val_bytes = _read_back(need, stream)
         caps = (pairs, rows, key_bytes, val_bytes)
         if into is None:
             trim = rows
@@ -795,19 +657,14 @@ def table_range_rows(file, table, positions, block_off, base=None, into=None, ca
         key_cap, val_cap = int(caps[2]), int(caps[3])
         dst = _mi_alloc(dev, item_cap, key_cap, val_cap)
     ws = plan(block_cap, row_cap)
-    _check(lib().lsm_table_range_rows(_ptr(file), file_len, C.byref(t), _ptr(block_off), n_blocks, C.byref(ps), n,
-                                      block_cap, row_cap, _ptr(base), _ptr(end), _ptr(ws), ws.numel(),
+    _check(lib().lsm_table_range_rows(*head, block_cap, row_cap, _ptr(base), _ptr(end), _ptr(ws), ws.numel(),
                                       _ptr(dst["key_off"]), _ptr(dst["val_off"]), _ptr(dst["keys"]), key_cap,
                                       _ptr(dst["vals"]), val_cap, _ptr(dst["seqno"]), _ptr(dst["vtype"]), item_cap,
                                       _ptr(result), st), "lsm_table_range_rows")
-    items = {f: dst[f] for f in ("keys", "key_off", "vals", "val_off", "seqno", "vtype")}
-    if trim is not None:
-        items.update(key_off=dst["key_off"][:trim + 1], val_off=dst["val_off"][:trim + 1],
-                     seqno=dst["seqno"][:trim], vtype=dst["vtype"][:trim])
+    items = _items_view(dst, trim)
     items.update(run_start=run_start, row_status=row_status[:n], end=end, need=need, result=result,
                  plan_result=plan_result)
     return items
-
 
 
 def seek(blocks, block_off, n_blocks, query_block, lo, lo_off, hi, hi_off, flags, stream=None):
@@ -834,11 +691,11 @@ def xxh3_128_file(data, length=None, offset=0, stream=None):
     (uint8 cuda tensor, readable 16 B past the end) -> (low, high) as Python ints."""
     torch = _torch()
     length = data.numel() - offset if length is None else length
-    ws = torch.empty(max(lib().lsm_xxh3_128_file_workspace_size(length), 256), dtype=torch.uint8, device=data.device)
+    ws = _workspace(max(lib().lsm_xxh3_128_file_workspace_size(length), 256), data.device, stream)
     out = torch.zeros(2, dtype=torch.int64, device=data.device)
     _check(lib().lsm_xxh3_128_file(C.c_void_p(data.data_ptr() + offset), length, _ptr(out), _ptr(ws), ws.numel(),
                                    _stream(stream)), "lsm_xxh3_128_file")
-    lo, hi = (int(x) & (2 ** 64 - 1) for x in out.cpu().tolist())
+    lo, hi = (x & (2 ** 64 - 1) for x in _read_back(out, stream))
     return lo, hi
 
 
@@ -891,8 +748,7 @@ class ChecksummedWriter:
             out = torch.zeros(2, dtype=torch.int64, device=self.device)
         _check(lib().lsm_xxh3_128_stream_digest(_ptr(self.state), _ptr(out), _stream(self.stream)),
                "lsm_xxh3_128_stream_digest")
-        self.stream.synchronize()
-        lo, hi = (int(x) & (2 ** 64 - 1) for x in out.cpu().tolist())
+        lo, hi = (x & (2 ** 64 - 1) for x in _read_back(out, self.stream))
         return lo, hi
 
 
@@ -943,8 +799,7 @@ class ChecksummedWriterSet:
             out = torch.zeros(2 * max(self.n, 1), dtype=torch.int64, device=self.device)
         _check(lib().lsm_xxh3_128_stream_digest_batch(_ptr(self.states), self.n, _ptr(out), _stream(self.stream)),
                "lsm_xxh3_128_stream_digest_batch")
-        self.stream.synchronize()
-        v = [int(x) & (2 ** 64 - 1) for x in out.cpu().tolist()]
+        v = [x & (2 ** 64 - 1) for x in _read_back(out, self.stream)]
         return [(v[2 * i], v[2 * i + 1]) for i in range(self.n)]
 
 
@@ -1011,13 +866,13 @@ def lz4_decompress_blocks(blocks, block_off, n_blocks=None, max_block_bytes=LZ4_
     dev = blocks.device
     out_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
     if n:
-        pws = torch.empty(lib().lsm_lz4_plan_workspace_size(n), dtype=torch.uint8, device=dev)
+        pws = _workspace(lib().lsm_lz4_plan_workspace_size(n), dev, stream)
         _check(lib().lsm_lz4_plan_output(_ptr(blocks), _ptr(block_off), n, max_block_bytes, _ptr(out_off), _ptr(pws),
                                          pws.numel(), _stream(stream)), "lsm_lz4_plan_output")
-    total = int(out_off[-1].item()) if n else 0
+    total = _read_back(out_off[-1], stream) if n else 0
     out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
     status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-    ws = torch.empty(lib().lsm_lz4_workspace_size(n), dtype=torch.uint8, device=dev)
+    ws = _workspace(lib().lsm_lz4_workspace_size(n), dev, stream)
     _check(lib().lsm_lz4_decompress_blocks(_ptr(blocks), _ptr(block_off), n, _ptr(out), _ptr(out_off),
                                            _ptr(status), _ptr(ws), ws.numel(), _stream(stream)),
            "lsm_lz4_decompress_blocks")
@@ -1042,7 +897,7 @@ def decode_lz4_blocks(blocks, block_off, n_blocks=None, expect_type=-1, item_cap
     dev = blocks.device
     frame_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
     if n:
-        pws = torch.empty(lib().lsm_lz4_plan_workspace_size(n), dtype=torch.uint8, device=dev)
+        pws = _workspace(lib().lsm_lz4_plan_workspace_size(n), dev, stream)
         if frames_cap is not None:
             _check(lib().lsm_lz4_plan_capped(_ptr(blocks), _ptr(block_off), n, max_block_bytes, 1, frames_cap,
                                              _ptr(frame_off), _ptr(pws), pws.numel(), _stream(stream)),
@@ -1053,10 +908,10 @@ def decode_lz4_blocks(blocks, block_off, n_blocks=None, expect_type=-1, item_cap
     if frames_cap is not None:
         total = frames_cap
     else:
-        total = int(frame_off[-1].item()) if n else 0
+        total = _read_back(frame_off[-1], stream) if n else 0
     frames = padded_bytes(total, dev)
-    zst = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-    ws = torch.empty(lib().lsm_lz4_workspace_size(n), dtype=torch.uint8, device=dev)
+    zst = _workspace(4 * max(n, 1), dev, stream).view(torch.int32)  # (the decompress statuses: not returned)
+    ws = _workspace(lib().lsm_lz4_workspace_size(n), dev, stream)
     _check(lib().lsm_lz4_decompress_framed(_ptr(blocks), _ptr(block_off), n, _ptr(frames), _ptr(frame_off),
                                            _ptr(zst), _ptr(ws), ws.numel(), _stream(stream)),
            "lsm_lz4_decompress_framed")
@@ -1066,8 +921,9 @@ def decode_lz4_blocks(blocks, block_off, n_blocks=None, expect_type=-1, item_cap
     out = d.alloc_outputs(item_cap, n, fields)
     d.decode(frames, frame_off, n, out, item_cap, expect_type,
              tuning=(0, 0, 0, DECODE_PAYLOAD_VERIFIED), stream=stream)
-    out["decode_status"] = out["status"].clone()  # (what a caller sees without the merge below)
-    out["status"] = torch.where(zst[:max(n, 1)] != 0, zst[:max(n, 1)], out["status"])
+    with torch.cuda.stream(stream):  # (the merge of the statuses follows the decode on its stream)
+        out["decode_status"] = out["status"].clone()  # (what a caller sees without the merge below)
+        out["status"] = torch.where(zst[:max(n, 1)] != 0, zst[:max(n, 1)], out["status"])
     out["frames"], out["frame_off"] = frames, frame_off
     return out
 
@@ -1092,11 +948,10 @@ def lz4_compress_blocks(blocks, block_off, n_blocks=None, in_status=None, out_ca
     buf = padded_bytes(out_cap, dev)
     out_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
     status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-    ws = torch.empty(lib().lsm_lz4_compress_workspace_size(n, blocks_bytes), dtype=torch.uint8, device=dev)
+    ws = _workspace(lib().lsm_lz4_compress_workspace_size(n, blocks_bytes), dev, stream)
     _check(lib().lsm_lz4_compress_blocks(_ptr(blocks), _ptr(block_off), n, _ptr(in_status), _ptr(buf), out_cap,
                                          _ptr(out_off), _ptr(status), _ptr(ws), ws.numel(), _stream(stream)),
            "lsm_lz4_compress_blocks")
-    ws.record_stream(torch.cuda.current_stream(dev) if stream is None else stream)
     return {"buf": buf, "block_off": out_off, "status": status[:n]}
 
 
@@ -1110,12 +965,10 @@ def materialize_keys(blocks, block_off, n_blocks, out, n_items=None, stream=None
     torch = _torch()
     dev = blocks.device
     if n_items is None:
-        n_items = out["key_off"].numel() if key_cap is not None else int(out["item_start"][n_blocks].item())
+        n_items = out["key_off"].numel() if key_cap is not None else _read_back(out["item_start"][n_blocks], stream)
     key_off = torch.zeros(n_items + 1, dtype=torch.int64, device=dev)
-    ps = LsmParsed()
-    for f, _ in PARSED_FIELDS:
-        setattr(ps, f, out[f].data_ptr() if f in out else None)
-    ws = torch.empty(lib().lsm_materialize_workspace_size(n_items), dtype=torch.uint8, device=dev)
+    ps = _parsed_struct(out)
+    ws = _workspace(lib().lsm_materialize_workspace_size(n_items), dev, stream)
     args = (_ptr(blocks), _ptr(block_off), n_blocks, _ptr(out["item_start"]), _ptr(out["status"]), C.byref(ps), n_items)
     _check(lib().lsm_materialize_plan(*args, _ptr(key_off), _ptr(ws), ws.numel(), _stream(stream)),
            "lsm_materialize_plan")
@@ -1125,7 +978,7 @@ def materialize_keys(blocks, block_off, n_blocks, out, n_items=None, stream=None
         _check(lib().lsm_materialize_keys_capped(*args, _ptr(key_off), _ptr(keys), key_cap, _ptr(result),
                                                  _stream(stream)), "lsm_materialize_keys_capped")
         return keys, key_off, result
-    total = int(key_off[-1].item()) if n_items else 0
+    total = _read_back(key_off[-1], stream) if n_items else 0
     keys = padded_bytes(total, dev)
     _check(lib().lsm_materialize_keys(*args, _ptr(key_off), _ptr(keys), _stream(stream)), "lsm_materialize_keys")
     return keys, key_off
@@ -1148,11 +1001,9 @@ def scan_table(file, file_len, tli_off, tli_size, two_level=False, global_seqno=
         item_cap = file_len // 3 + 1
     out = Decoder(dev).alloc_outputs(item_cap, cap_blocks, fields)
     block_off = torch.zeros(cap_blocks + 1, dtype=torch.int64, device=dev)
-    ws = torch.empty(lib().lsm_scan_workspace_size(cap_blocks), dtype=torch.uint8, device=dev)
-    ps = LsmParsed()
-    for f, _ in PARSED_FIELDS:
-        setattr(ps, f, out[f].data_ptr() if f in out else None)
-    t = LsmTableScan(tli_off, tli_size, int(bool(two_level)), global_seqno & (2 ** 64 - 1), block_count)
+    ws = _workspace(lib().lsm_scan_workspace_size(cap_blocks), dev, stream)
+    ps = _parsed_struct(out)
+    t = _table_struct({"tli_off": tli_off, "tli_size": tli_size, "two_level": two_level}, global_seqno, block_count)
     if not sync:
         d_nb = torch.zeros(1, dtype=torch.int32, device=dev)
         d_ts = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -1207,14 +1058,11 @@ def cut_blocks_device(items_or_offsets, block_size, n_items=None, extra=0, strea
         cap = int(n_items)
     starts = torch.empty(cap + 1, dtype=torch.int32, device=dev)
     res = torch.empty(2, dtype=torch.int64, device=dev)  # [n_blocks, status]
-    ws = torch.empty(lib().lsm_cut_workspace_size(cap), dtype=torch.uint8, device=dev)
+    ws = _workspace(lib().lsm_cut_workspace_size(cap), dev, stream)
     _check(lib().lsm_cut_blocks_device(_ptr(key_off), _ptr(val_off), cap, _ptr(d_n), extra, block_size,
                                        _ptr(starts), max(cap, 1), _ptr(res[0:]), _ptr(res[1:]), _ptr(ws),
                                        ws.numel(), _stream(stream)), "lsm_cut_blocks_device")
-    ws.record_stream(torch.cuda.current_stream(dev) if stream is None else stream)
-    if stream is not None:
-        stream.synchronize()
-    nb, status = res.cpu().tolist()
+    nb, status = _read_back(res, stream)
     _check(status & 0xFFFFFFFF, "lsm_cut_blocks_device (device status)")
     return starts[:nb + 1]
 
@@ -1227,24 +1075,20 @@ def index_entries(items, starts, block_off, n_blocks, base_offset=0, key_cap=Non
     them.  key_cap defaults to the items' key arena, which always suffices.  No host synchronisation."""
     torch = _torch()
     dev = items["keys"].device
-    n = items["seqno"].numel()
     if key_cap is None:
         key_cap = items["keys"].numel()
-    it = LsmItems()
-    it.keys, it.key_off, it.seqno, it.n_items = items["keys"].data_ptr(), items["key_off"].data_ptr(), \
-        items["seqno"].data_ptr(), n
+    it, held = _items_struct(items, ("keys", "key_off", "seqno"))
     out = {"keys": torch.zeros(key_cap + LSM_INPUT_PADDING, dtype=torch.uint8, device=dev),
            "key_off": torch.empty(n_blocks + 1, dtype=torch.int64, device=dev),
            "seqno": torch.empty(n_blocks, dtype=torch.int64, device=dev),
            "handle_off": torch.empty(n_blocks, dtype=torch.int64, device=dev),
            "handle_size": torch.empty(n_blocks, dtype=torch.int32, device=dev),
            "result": torch.empty(1, dtype=torch.int32, device=dev)}
-    ws = torch.empty(lib().lsm_index_entries_workspace_size(n_blocks), dtype=torch.uint8, device=dev)
+    ws = _workspace(lib().lsm_index_entries_workspace_size(n_blocks), dev, stream)
     _check(lib().lsm_index_entries(C.byref(it), _ptr(starts), _ptr(block_off), n_blocks, base_offset,
                                    _ptr(out["keys"]), key_cap, _ptr(out["key_off"]), _ptr(out["seqno"]),
                                    _ptr(out["handle_off"]), _ptr(out["handle_size"]), _ptr(out["result"]), _ptr(ws),
                                    ws.numel(), _stream(stream)), "lsm_index_entries")
-    ws.record_stream(torch.cuda.current_stream(dev) if stream is None else stream)
     return out
 
 
@@ -1341,6 +1185,35 @@ def items_to_device(items_np, device="cuda", off32=False):
 MERGE_MAX_RUNS, MERGE_EVICT_TOMBSTONES, MERGE_ZERO_SEQNOS = 64, 1, 2
 
 
+def _run_start(items, run_start):
+    """run_start as an int64 tensor on the items' device (a host sequence is uploaded)."""
+    if hasattr(run_start, "data_ptr"):
+        return run_start
+    torch = _torch()
+    return torch.tensor(list(run_start), dtype=torch.int64, device=items["keys"].device)
+
+
+def _merge_io(items, tail, tail_len, n_status):
+    """What lsm_merge_runs and lsm_merge_read share: (the input lsm_items, its stand-ins to keep
+    alive, the output dict).  The outputs are sized for the input and listed in the order both
+    calls take them: the items-shaped arrays, src, the int64 [tail_len] array named `tail`
+    (n_out / group_start), status (int32 [n_status])."""
+    torch = _torch()
+    dev = items["keys"].device
+    it, held = _items_struct(items)
+    n = it.n_items
+    out = {"keys": torch.empty(items["keys"].numel() + LSM_INPUT_PADDING, dtype=torch.uint8, device=dev),
+           "key_off": torch.empty(n + 1, dtype=torch.int64, device=dev),
+           "vals": torch.empty(items["vals"].numel() + LSM_INPUT_PADDING, dtype=torch.uint8, device=dev),
+           "val_off": torch.empty(n + 1, dtype=torch.int64, device=dev),
+           "seqno": torch.empty(max(n, 1), dtype=torch.int64, device=dev),
+           "vtype": torch.empty(max(n, 1), dtype=torch.uint8, device=dev),
+           "src": torch.empty(max(n, 1), dtype=torch.int32, device=dev),
+           tail: torch.empty(tail_len, dtype=torch.int64, device=dev),
+           "status": torch.empty(max(n_status, 1), dtype=torch.int32, device=dev)}
+    return it, held, out
+
+
 def merge_runs(items, run_start, gc_seqno_threshold=0, evict_tombstones=False, zero_seqnos=False, stream=None):
     """CompactionStream::new(Merger::new(runs), gc_seqno_threshold).evict_tombstones(..).zero_seqnos(..)
     (merge.rs:34-100, compaction/stream.rs:46-221) on the device.  items: device dict as
@@ -1349,38 +1222,13 @@ def merge_runs(items, run_start, gc_seqno_threshold=0, evict_tombstones=False, z
     vtype, sized for the input: the first n_out items / n_out + 1 offsets are defined) plus
     src (int32: input index of each output item), n_out (int64 [1], on the device) and status
     (int32 [n_runs]).  No host synchronisation."""
-    torch = _torch()
-    dev = items["keys"].device
-    if not hasattr(run_start, "data_ptr"):
-        run_start = torch.tensor(list(run_start), dtype=torch.int64, device=dev)
-    n_runs = run_start.numel() - 1
-    n = items["seqno"].numel()
-    it = LsmItems()
-    held = []
-    for f in ("keys", "key_off", "vals", "val_off", "seqno", "vtype"):
-        t = items[f]
-        if t.numel() == 0:  # (an empty tensor has no address; the library wants every array non-NULL)
-            t = torch.zeros(1, dtype=t.dtype, device=dev)
-            held.append(t)
-        setattr(it, f, t.data_ptr())
-    it.n_items = n
-    out = {"keys": torch.empty(items["keys"].numel() + LSM_INPUT_PADDING, dtype=torch.uint8, device=dev),
-           "vals": torch.empty(items["vals"].numel() + LSM_INPUT_PADDING, dtype=torch.uint8, device=dev),
-           "key_off": torch.empty(n + 1, dtype=torch.int64, device=dev),
-           "val_off": torch.empty(n + 1, dtype=torch.int64, device=dev),
-           "seqno": torch.empty(max(n, 1), dtype=torch.int64, device=dev),
-           "vtype": torch.empty(max(n, 1), dtype=torch.uint8, device=dev),
-           "src": torch.empty(max(n, 1), dtype=torch.int32, device=dev),
-           "n_out": torch.empty(1, dtype=torch.int64, device=dev),
-           "status": torch.empty(max(n_runs, 1), dtype=torch.int32, device=dev)}
-    ws = torch.empty(lib().lsm_merge_workspace_size(n, max(n_runs, 0)), dtype=torch.uint8, device=dev)
+    run_start = _run_start(items, run_start)
+    n_runs = max(run_start.numel() - 1, 0)
+    it, held, out = _merge_io(items, "n_out", 1, n_runs)
+    ws = _workspace(lib().lsm_merge_workspace_size(it.n_items, n_runs), run_start.device, stream)
     flags = (MERGE_EVICT_TOMBSTONES if evict_tombstones else 0) | (MERGE_ZERO_SEQNOS if zero_seqnos else 0)
-    _check(lib().lsm_merge_runs(C.byref(it), _ptr(run_start), max(n_runs, 0), gc_seqno_threshold & (2 ** 64 - 1),
-                                flags, _ptr(out["keys"]), _ptr(out["key_off"]), _ptr(out["vals"]),
-                                _ptr(out["val_off"]), _ptr(out["seqno"]), _ptr(out["vtype"]), _ptr(out["src"]),
-                                _ptr(out["n_out"]), _ptr(out["status"]), _ptr(ws), ws.numel(), _stream(stream)),
-           "lsm_merge_runs")
-    ws.record_stream(torch.cuda.current_stream(dev) if stream is None else stream)
+    _check(lib().lsm_merge_runs(C.byref(it), _ptr(run_start), n_runs, gc_seqno_threshold & (2 ** 64 - 1), flags,
+                                *map(_ptr, out.values()), _ptr(ws), ws.numel(), _stream(stream)), "lsm_merge_runs")
     return out
 
 
@@ -1399,37 +1247,13 @@ def merge_read(items, run_start, n_groups, n_sources, snapshot, group_seqno=None
     Returns merge_runs' dict with group_start (int64 [n_groups + 1]: group g's rows are
     [group_start[g], group_start[g + 1])) in place of n_out, and status of [n_groups].
     No host synchronisation."""
-    torch = _torch()
-    dev = items["keys"].device
-    if not hasattr(run_start, "data_ptr"):
-        run_start = torch.tensor(list(run_start), dtype=torch.int64, device=dev)
-    n = items["seqno"].numel()
-    it = LsmItems()
-    held = []
-    for f in ("keys", "key_off", "vals", "val_off", "seqno", "vtype"):
-        t = items[f]
-        if t.numel() == 0:  # (an empty tensor has no address; the library wants every array non-NULL)
-            t = torch.zeros(1, dtype=t.dtype, device=dev)
-            held.append(t)
-        setattr(it, f, t.data_ptr())
-    it.n_items = n
-    out = {"keys": torch.empty(items["keys"].numel() + LSM_INPUT_PADDING, dtype=torch.uint8, device=dev),
-           "vals": torch.empty(items["vals"].numel() + LSM_INPUT_PADDING, dtype=torch.uint8, device=dev),
-           "key_off": torch.empty(n + 1, dtype=torch.int64, device=dev),
-           "val_off": torch.empty(n + 1, dtype=torch.int64, device=dev),
-           "seqno": torch.empty(max(n, 1), dtype=torch.int64, device=dev),
-           "vtype": torch.empty(max(n, 1), dtype=torch.uint8, device=dev),
-           "src": torch.empty(max(n, 1), dtype=torch.int32, device=dev),
-           "group_start": torch.empty(n_groups + 1, dtype=torch.int64, device=dev),
-           "status": torch.empty(max(n_groups, 1), dtype=torch.int32, device=dev)}
-    ws = torch.empty(lib().lsm_merge_read_workspace_size(n, n_groups, n_sources), dtype=torch.uint8, device=dev)
+    run_start = _run_start(items, run_start)
+    it, held, out = _merge_io(items, "group_start", n_groups + 1, n_groups)
+    ws = _workspace(lib().lsm_merge_read_workspace_size(it.n_items, n_groups, n_sources), run_start.device, stream)
     flags = MERGE_READ_KEEP_TOMBSTONES if keep_tombstones else 0
     _check(lib().lsm_merge_read(C.byref(it), _ptr(run_start), n_groups, n_sources, snapshot & (2 ** 64 - 1),
-                                _ptr(group_seqno), _ptr(in_status), flags, _ptr(out["keys"]),
-                                _ptr(out["key_off"]), _ptr(out["vals"]), _ptr(out["val_off"]), _ptr(out["seqno"]),
-                                _ptr(out["vtype"]), _ptr(out["src"]), _ptr(out["group_start"]),
-                                _ptr(out["status"]), _ptr(ws), ws.numel(), _stream(stream)), "lsm_merge_read")
-    ws.record_stream(torch.cuda.current_stream(dev) if stream is None else stream)
+                                _ptr(group_seqno), _ptr(in_status), flags, *map(_ptr, out.values()), _ptr(ws),
+                                ws.numel(), _stream(stream)), "lsm_merge_read")
     out["status"] = out["status"][:n_groups]
     return out
 
@@ -1461,17 +1285,13 @@ def range_read(tables, lo, lo_off, hi, hi_off, flags, snapshot, group_seqno=None
         cap = min(n * nb, RANGE_ROWS_AUTO_PAIRS)
         needs.append((cap, table_range_rows(t["file"], t, pos, t["block_off"], caps=(cap, 0, 0, 0), stream=stream,
                                             n_queries=n)["need"]))
-    if stream is not None:
-        stream.synchronize()
-    needs = [(cap, need.cpu().tolist()) for cap, need in needs]
+    needs = [(cap, _read_back(need, stream)) for cap, need in needs]
     for s, (cap, need) in enumerate(needs):
         if need[0] > cap:
             t = tables[s]
             again = table_range_rows(t["file"], t, positions[s], t["block_off"], caps=(need[0], 0, 0, 0),
                                      stream=stream, n_queries=n)["need"]
-            if stream is not None:
-                stream.synchronize()
-            needs[s] = (need[0], again.cpu().tolist())
+            needs[s] = (need[0], _read_back(again, stream))
     rows, key_bytes, val_bytes = (sum(need[k] for _, need in needs) for k in (1, 2, 3))
     dst = _mi_alloc(dev, rows, key_bytes, val_bytes)
     cursor, run_start, row_status = None, [], []
@@ -1482,10 +1302,8 @@ def range_read(tables, lo, lo_off, hi, hi_off, flags, snapshot, group_seqno=None
         cursor = res["end"]
         run_start.append(res["run_start"][:n] if s + 1 < n_src else res["run_start"])
         row_status.append(res["row_status"])
-    items = {"keys": dst["keys"], "key_off": dst["key_off"][:rows + 1], "vals": dst["vals"],
-             "val_off": dst["val_off"][:rows + 1], "seqno": dst["seqno"][:rows], "vtype": dst["vtype"][:rows]}
     row_status = torch.cat(row_status)
-    out = merge_read(items, torch.cat(run_start), n, n_src, snapshot, group_seqno=group_seqno,
+    out = merge_read(_items_view(dst, rows), torch.cat(run_start), n, n_src, snapshot, group_seqno=group_seqno,
                      in_status=row_status, keep_tombstones=keep_tombstones, stream=stream)
     out["row_status"] = row_status
     return out
@@ -1494,9 +1312,7 @@ def range_read(tables, lo, lo_off, hi, hi_off, flags, snapshot, group_seqno=None
 def _mi_args(blocks, block_off, n_blocks, out):
     """The leading arguments lsm_materialize_items_plan and lsm_materialize_items share (and the
     struct they point into, which the caller keeps alive)."""
-    ps = LsmParsed()
-    for f, _ in PARSED_FIELDS:
-        setattr(ps, f, out[f].data_ptr() if f in out else None)
+    ps = _parsed_struct(out)
     d_nb = n_blocks if hasattr(n_blocks, "data_ptr") else None
     nb = out["item_start"].numel() - 1 if d_nb is not None else int(n_blocks)
     return (_ptr(blocks), _ptr(block_off), nb, _ptr(d_nb), _ptr(out["item_start"]), _ptr(out["status"]),
@@ -1504,12 +1320,10 @@ def _mi_args(blocks, block_off, n_blocks, out):
 
 
 def _mi_plan(args, base, dst, item_cap, end, result, stream):
-    torch = _torch()
-    ws = torch.empty(lib().lsm_materialize_items_workspace_size(args[7]), dtype=torch.uint8, device=end.device)
+    ws = _workspace(lib().lsm_materialize_items_workspace_size(args[7]), end.device, stream)
     _check(lib().lsm_materialize_items_plan(*args, _ptr(base), _ptr(dst["key_off"]), _ptr(dst["val_off"]), item_cap,
                                             _ptr(end), _ptr(result), _ptr(ws), ws.numel(), _stream(stream)),
            "lsm_materialize_items_plan")
-    ws.record_stream(torch.cuda.current_stream(end.device) if stream is None else stream)
 
 
 def _mi_gather(args, base, end, dst, caps, result, stream):
@@ -1566,16 +1380,11 @@ def materialize_items(blocks, block_off, n_blocks, out, base=None, into=None, ca
             raise LsmError("materialize_items: a base needs `into` or `caps` (the outputs it already fills)")
         dst = _mi_alloc(dev, args[7])
         _mi_plan(args, None, dst, args[7], end, plan_result, stream)
-        if stream is not None:
-            stream.synchronize()
-        trim, key_cap, val_cap = end.cpu().tolist()
+        trim, key_cap, val_cap = _read_back(end, stream)
         dst["keys"], dst["vals"] = padded_bytes(key_cap, dev), padded_bytes(val_cap, dev)
         caps = (args[7], key_cap, val_cap)
     _mi_gather(args, base, end, dst, caps, result, stream)
-    items = {f: dst[f] for f in ("keys", "key_off", "vals", "val_off", "seqno", "vtype")}
-    if trim is not None:
-        items.update(key_off=dst["key_off"][:trim + 1], val_off=dst["val_off"][:trim + 1],
-                     seqno=dst["seqno"][:trim], vtype=dst["vtype"][:trim])
+    items = _items_view(dst, trim)
     items.update(end=end, result=result, plan_result=plan_result)
     return items
 
@@ -1598,15 +1407,11 @@ def tables_to_runs(tables, stream=None):
     result = torch.zeros(nt, dtype=torch.int32, device=dev)
     for t, (a, _) in enumerate(calls):
         _mi_plan(a, cursor[t], dst, item_cap, cursor[t + 1], plan_result[t:], stream)
-    if stream is not None:
-        stream.synchronize()
-    n, key_cap, val_cap = cursor[nt].cpu().tolist()
+    n, key_cap, val_cap = _read_back(cursor[nt], stream)
     dst["keys"], dst["vals"] = padded_bytes(key_cap, dev), padded_bytes(val_cap, dev)
     for t, (a, _) in enumerate(calls):
         _mi_gather(a, cursor[t], cursor[t + 1], dst, (item_cap, key_cap, val_cap), result[t:], stream)
-    items = {"keys": dst["keys"], "key_off": dst["key_off"][:n + 1], "vals": dst["vals"],
-             "val_off": dst["val_off"][:n + 1], "seqno": dst["seqno"][:n], "vtype": dst["vtype"][:n],
-             "result": result, "plan_result": plan_result}
+    items = dict(_items_view(dst, n), result=result, plan_result=plan_result)
     return items, cursor[:, 0].contiguous()
 
 

@@ -25,6 +25,94 @@ def declared_functions():
     return sorted(set(re.findall(r"\b(lsm_[a-z0-9_]+)\s*\(", text)))
 
 
+C_SCALARS = {"int": "c_int", "size_t": "c_size_t", "float": "c_float", "uint8_t": "c_uint8", "uint16_t": "c_uint16",
+             "uint32_t": "c_uint32", "uint64_t": "c_uint64", "int8_t": "c_int8", "int16_t": "c_int16",
+             "int32_t": "c_int32", "int64_t": "c_int64"}
+STRUCT_MIRRORS = {"lsm_items": "LsmItems", "lsm_items32": "LsmItems32", "lsm_parsed_items": "LsmParsed",
+                  "lsm_parsed_items16": "LsmParsed16", "lsm_block_params": "LsmBlockParams",
+                  "lsm_point_result": "LsmPointResult", "lsm_decode_tuning": "LsmDecodeTuning",
+                  "lsm_table_scan": "LsmTableScan", "lsm_range_result": "LsmRangeResult",
+                  "lsm_range_positions": "LsmRangePositions"}
+
+
+def _header_statements():
+    """The header without comments and preprocessor lines, as (struct bodies, other statements):
+    a parse of its own, by statements, that shares nothing with lsmgpu.py's."""
+    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "lsmgpu.h").read_text(), flags=re.S)
+    text = "\n".join(line for line in text.splitlines() if not line.lstrip().startswith("#"))
+    text = text.replace('extern "C" {', "")
+    structs = {m.group(3): m.group(2) for m in re.finditer(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*(\w+)\s*;", text)}
+    rest = re.sub(r"\{[^{}]*\}", "", text)
+    return structs, [" ".join(s.split()) for s in rest.split(";")]
+
+
+def _declarator(decl):
+    """'const uint8_t* d_blocks' -> ('uint8_t', True, 'd_blocks'): base type, is a pointer, name."""
+    words = decl.replace("*", " * ").split()
+    name, words = words[-1], [w for w in words[:-1] if w != "const"]
+    assert words and words.count("*") <= 1 and words[0] != "*", decl
+    return words[0], "*" in words, name
+
+
+def declared_prototypes():
+    """{function: ((base, is pointer), [(base, is pointer, parameter name), ...])} of the header."""
+    protos = {}
+    for stmt in _header_statements()[1]:
+        if "(" not in stmt:
+            continue
+        head, params = stmt[:stmt.index("(")], stmt[stmt.index("(") + 1:stmt.rindex(")")]
+        base, ptr, name = _declarator(head)
+        params = [] if params.strip() == "void" else [_declarator(p) for p in params.split(",")]
+        protos[name] = ((base, ptr), params)
+    return protos
+
+
+def test_signatures_follow_the_header(L):
+    """restype and argtypes of every declared function are those of its prototype: the parameter
+    count, each scalar's ctypes type, each pointer c_void_p or POINTER(the Structure that mirrors
+    the struct it points to); so a uint64_t cannot become a c_uint32 unnoticed."""
+    import ctypes as C
+    lib = L.lib()
+    protos = declared_prototypes()
+    assert sorted(protos) == declared_functions() and len(protos) >= 69
+    for name, ((rbase, rptr), params) in protos.items():
+        fn = getattr(lib, name)
+        want = C.c_char_p if (rbase, rptr) == ("char", True) else getattr(C, C_SCALARS[rbase])
+        assert not rptr or rbase == "char", name
+        assert fn.restype is want, name
+        assert len(fn.argtypes) == len(params), name
+        for (base, ptr, pname), at in zip(params, fn.argtypes):
+            if not ptr:
+                assert at is getattr(C, C_SCALARS[base]), (name, pname)
+            elif base in STRUCT_MIRRORS:  # (a typed struct pointer stays typed)
+                assert issubclass(at, C._Pointer) and at._type_ is getattr(L, STRUCT_MIRRORS[base]), (name, pname)
+            else:
+                assert at is C.c_void_p and (base == "void" or base in C_SCALARS), (name, pname)
+
+
+def test_struct_mirrors_follow_the_header(L):
+    """Each of the header's ten structs has its Structure: the same field names in the same order,
+    every scalar field of its C type's ctypes type, every pointer field a c_void_p."""
+    import ctypes as C
+    structs = _header_statements()[0]
+    assert set(structs) == set(STRUCT_MIRRORS) and len(structs) == 10
+    for cname, body in structs.items():
+        fields = [_declarator(" ".join(f.split())) for f in body.split(";") if f.strip()]
+        mirror = getattr(L, STRUCT_MIRRORS[cname])._fields_
+        assert [n for n, _ in mirror] == [n for _, _, n in fields], cname
+        for (base, ptr, fname), (_, ft) in zip(fields, mirror):
+            assert ft is (C.c_void_p if ptr else getattr(C, C_SCALARS[base])), (cname, fname)
+
+
+def test_unknown_header_type_is_an_error(L):
+    """A C type the binding has no mapping for is an LsmError that names the prototype, not a guess."""
+    import ctypes as C
+    assert L._c_type("lsm_f", "const uint32_t* ") is C.c_void_p and L._c_type("lsm_f", "uint64_t ") is C.c_uint64
+    for ctype in ("double ", "lsm_unknown* ", "const char* ", "uint8_t** ", "lsm_items ", ""):
+        with pytest.raises(L.LsmError, match="lsm_f"):
+            L._c_type("lsm_f", ctype)
+
+
 def test_header_declares_expected_entry_points():
     fns = declared_functions()
     for f in ("lsm_decode_blocks", "lsm_encode_blocks", "lsm_cut_blocks", "lsm_xxh3_128_batch",
