@@ -60,7 +60,10 @@
  *                      <- the items Table::range yields  src/table/mod.rs:391-422, iter.rs:272-290
  *                         (the owned InternalValue with seqno + global_seqno of every row between the two
  *                         positions of lsm_table_range)
- *   lsm_merge_runs     <- Merger::new / next       src/merge.rs:34-100
+ *   lsm_table_get_framed / lsm_table_range_framed / lsm_table_range_rows_plan_framed / lsm_table_range_rows_framed
+ *                      <- the same three on a table whose data blocks are LZ4: load_block through the block
+ *                         cache  src/table/util.rs:79-86, Block::from_file  block/mod.rs:131-182
+ *   lsm_merge_runs     <- Merger::new / next      src/merge.rs:34-100
  *                         CompactionStream          src/compaction/stream.rs:46-221
  *                         InternalKey Ord           src/key.rs:59-72
  *                         (as composed in compaction/worker.rs:149-182,389-390)
@@ -751,8 +754,8 @@ int lsm_scan_table_async(const uint8_t* d_file, uint64_t file_len, const lsm_tab
  * index block with data_length != uncompressed_length, i.e. an LZ4 table, or a Bloom
  * k > LSM_BLOOM_MAX_K); LSM_BAD_MAGIC for a malformed Bloom image header.
  * Limits: partitioned filters (the TOC's "filter_tli") are not supported (the reference
- * leaves the unpinned form unimplemented, mod.rs:265-266); LZ4-compressed tables are not
- * supported.  Payload checksums are not recomputed (the contract of
+ * leaves the unpinned form unimplemented, mod.rs:265-266); LZ4-compressed tables are
+ * read by lsm_table_get_framed.  Payload checksums are not recomputed (the contract of
  * lsm_point_read_blocks: blocks as loaded by Block::from_file): verify the regions once
  * with lsm_decode_blocks or lsm_xxh3_128_batch.  No byte outside
  * d_file[0 .. file_len + LSM_INPUT_PADDING) is read, whatever the file holds.
@@ -926,7 +929,7 @@ int lsm_table_range(const uint8_t* d_file, uint64_t file_len, const lsm_table_sc
  * workspace below lsm_table_range_rows_workspace_size(n_queries, block_cap, row_cap),
  * d_end == d_base.  Both calls are asynchronous on `stream`, do no host synchronisation,
  * have no wait between workgroups and may be captured into a graph on one stream.
- * Not built: `limit`, the reverse and mixed drains, LZ4 tables.  The MVCC read filter over
+ * Not built: `limit`, the reverse and mixed drains (LZ4 tables: the _framed forms below).  The MVCC read filter over
  * the rows of several tables is lsm_merge_read. */
 typedef struct lsm_range_positions {
     const uint8_t* outcome;      /* LSM_RANGE_* */
@@ -951,6 +954,99 @@ int lsm_table_range_rows(const uint8_t* d_file, uint64_t file_len, const lsm_tab
                          uint64_t* d_out_val_off, uint8_t* d_out_keys, uint64_t key_cap, uint8_t* d_out_vals,
                          uint64_t val_cap, uint64_t* d_out_seqno, uint8_t* d_out_vtype, uint64_t out_item_cap,
                          int32_t* d_result, void* stream);
+
+/* ---- the readers on an LZ4 table: data blocks through inflated frames -------------
+ * lsm_table_get, lsm_table_range and lsm_table_range_rows for a table whose data blocks
+ * are LZ4 (the default data_block_compression_policy below level 0), the reference's
+ * pattern: load_block finds the decompressed block by the handle's offset in the block
+ * cache, Block::from_file verifies and decompresses on a miss (src/table/util.rs:79-86,
+ * block/mod.rs:131-182).  Here the cache is fully populated up front: an lsm_table_frames
+ * view (a host struct of device arrays, passed as const void*) is what
+ * lsm_lz4_plan_framed + lsm_lz4_decompress_framed leave when run over the table's stored
+ * data-block offsets as their d_block_off: stored_off = that d_block_off, frame_off =
+ * the plan's d_out_off, frames = the decompress's d_out, frame_status = its d_status,
+ * frames_len = frame_off[n_blocks].  Frame b = Header' || payload with data_length =
+ * uncompressed_length and the stored checksum verified, which is what the block readers
+ * accept.  Index blocks, the TLI and the filter block are read from d_file, uncompressed,
+ * as by the plain calls (index_block_compression_policy is None).
+ * The data-block load of a handle (off, size) the index yields, in this order (it decides
+ * which fault a query reports):
+ *  1. the handle lies in the file, as in the plain calls: size < 33, a wrap-around or
+ *     off + size > file_len: LSM_TRUNCATED;
+ *  2. the ordinal: b = the last b < n_blocks with stored_off[b] <= off, by binary search
+ *     (at most ceil(log2 n_blocks) steps whatever the array holds); stored_off[b] != off,
+ *     stored_off[b+1] != off + size or n_blocks == 0: LSM_BAD_ARG (the view is not this
+ *     table's; lsm_table_range's rule for ordinals);
+ *  3. frame_status[b] != LSM_OK: that status, the Err of Block::from_file (header,
+ *     LSM_CKSUM of the stored bytes, LSM_DECOMPRESS), before the type test as in the
+ *     reference;
+ *  4. the frame's extent: frame_off[b+1] < frame_off[b], a frame shorter than 33 bytes or
+ *     one ending past frames_len: LSM_TRUNCATED;
+ *  5. the plain calls' load_block on the frame: header fields, type Data
+ *     (LSM_TYPE_MISMATCH), data_length == frame size - 33 (LSM_TRUNCATED), uncompressed
+ *     (LSM_UNSUPPORTED), trailer (LSM_PARSE); then the same point read / seek.
+ * No byte outside d_file[0 .. file_len + LSM_INPUT_PADDING) and
+ * frames[0 .. frames_len + LSM_INPUT_PADDING) is read, whatever the file and the view
+ * hold.  Identity view: frames = d_file, frame_off = stored_off, frame_status = NULL,
+ * frames_len = file_len over an uncompressed table gives exactly the plain calls' answers.
+ * lsm_table_get_framed: lsm_table_get's parameters, then the view and d_hit_block.
+ *   d_hit_block_off / d_hit_block_size report the STORED handle, d_hit_block (may be NULL)
+ *   its ordinal; val_off / val_len are relative to the frame's payload, so a hit's value
+ *   is frames[frame_off[hit_block] + 33 + val_off ..).  Outcomes and statuses as
+ *   lsm_table_get, plus those of steps 2-4.
+ * lsm_table_range_framed: lsm_table_range's parameters with (d_data_block_off,
+ *   n_data_blocks) replaced by the view (required).  first_block / last_block are ordinals
+ *   in stored_off (the loads' own: no second search), the handles reported are the stored
+ *   ones, first_item / last_item index the decompressed blocks.
+ * lsm_table_range_rows_plan_framed / lsm_table_range_rows_framed: the plain calls without
+ *   d_file, file_len, d_data_block_off and n_data_blocks, the view after `table`.  Block b
+ *   is frame b; positions come from lsm_table_range_framed over the same view.  Every
+ *   touched block is checked as by lsm_table_range_rows with frame_status[b] first
+ *   (a non-OK entry is the block's status and takes part in the lowest-ordinal rule; a
+ *   value outside 1..255 counts as LSM_BAD_ARG), then (1) the handle test on frame_off
+ *   against frames_len, (2)-(5) unchanged.  Row descriptors address the frame arena.
+ *   Workspace size function, caps, cursor and all-or-nothing rules are the plain calls'.
+ * All four are asynchronous on `stream`, do no host synchronisation, have no wait between
+ * workgroups and may be captured into a graph on one stream.  LSM_BAD_ARG (before any
+ * device work): a NULL view, a NULL stored_off / frames / frame_off, frames not 16-byte
+ * aligned, and the plain calls' own argument errors.
+ * Not built: selective inflate (the view holds every data block of the table),
+ * compressed index blocks. */
+struct lsm_table_frames {
+    const uint64_t* stored_off;   /* device [n_blocks + 1]: the table's data-block offsets as stored in the file */
+    const uint8_t*  frames;       /* device, 16-byte aligned, readable LSM_INPUT_PADDING bytes past frames_len */
+    const uint64_t* frame_off;    /* device [n_blocks + 1]: frame b = frames[frame_off[b] .. frame_off[b+1]) */
+    const int32_t*  frame_status; /* device [n_blocks], lsm_lz4_decompress_framed's d_status; NULL = every frame LSM_OK */
+    uint64_t frames_len;          /* bytes of `frames` the kernels may read (plus the padding) */
+    uint32_t n_blocks;
+};
+typedef struct lsm_table_frames lsm_table_frames;
+int lsm_table_get_framed(const uint8_t* d_file, uint64_t file_len, const lsm_table_scan* table,
+                         uint64_t filter_off, uint32_t filter_size, uint64_t lowest_seqno,
+                         const uint8_t* d_needles, const uint64_t* d_needle_off, const uint64_t* d_snapshot,
+                         const uint64_t* d_key_hash, const uint8_t* d_active, uint32_t n_queries,
+                         const lsm_point_result* d_out, uint64_t* d_hit_block_off, uint32_t* d_hit_block_size,
+                         uint8_t* d_outcome, int32_t* d_status,
+                         const void* frames /* const lsm_table_frames* */, uint32_t* d_hit_block, void* stream);
+int lsm_table_range_framed(const uint8_t* d_file, uint64_t file_len, const lsm_table_scan* table,
+                           const uint8_t* d_lo, const uint64_t* d_lo_off, const uint8_t* d_hi,
+                           const uint64_t* d_hi_off, const uint8_t* d_flags, uint32_t n_queries,
+                           const void* frames /* const lsm_table_frames* */,
+                           const void* d_out /* const lsm_range_result* */, uint8_t* d_outcome, int32_t* d_status,
+                           void* stream);
+int lsm_table_range_rows_plan_framed(const lsm_table_scan* table, const void* frames /* const lsm_table_frames* */,
+                                     const void* pos /* const lsm_range_positions* */, uint32_t n_queries,
+                                     uint64_t block_cap, uint64_t row_cap, const uint64_t* d_base,
+                                     uint64_t* d_run_start, uint64_t* d_end, uint64_t* d_need,
+                                     int32_t* d_row_status, int32_t* d_result, void* d_workspace,
+                                     size_t workspace_bytes, void* stream);
+int lsm_table_range_rows_framed(const lsm_table_scan* table, const void* frames /* const lsm_table_frames* */,
+                                const void* pos /* const lsm_range_positions* */, uint32_t n_queries,
+                                uint64_t block_cap, uint64_t row_cap, const uint64_t* d_base, const uint64_t* d_end,
+                                void* d_workspace, size_t workspace_bytes, uint64_t* d_out_key_off,
+                                uint64_t* d_out_val_off, uint8_t* d_out_keys, uint64_t key_cap, uint8_t* d_out_vals,
+                                uint64_t val_cap, uint64_t* d_out_seqno, uint8_t* d_out_vtype,
+                                uint64_t out_item_cap, int32_t* d_result, void* stream);
 
 /* ---- merge of sorted runs with compaction GC ----------------------------------
  * CompactionStream::new(Merger::new(runs), gc_seqno_threshold)

@@ -39,6 +39,7 @@
 namespace lsmgpu {
 
 struct TableGetParams {
+  static constexpr bool kFramed = false;
   const uint8_t* file;
   uint64_t file_len;
   uint64_t tli_off;
@@ -61,7 +62,17 @@ struct TableGetParams {
   int32_t* status;
 };
 
-__global__ __launch_bounds__(256) void table_get_kernel(TableGetParams P) {
+// lsm_table_get_framed: the index, the TLI and the filter from the file, every data
+// block from the view's frame of its handle (load_data_block, table_index.hpp).
+struct TableGetFramedParams : TableGetParams {
+  static constexpr bool kFramed = true;
+  FramesView view;
+  uint32_t* hit_block;
+};
+
+// The body of both kernels (the plain one compiles to the code it had as a kernel of its own).
+template <class Params>
+__device__ __forceinline__ void table_get_query(const Params& P) {
   const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= P.n) return;
   if (P.active && !P.active[q]) return;
@@ -77,7 +88,7 @@ __global__ __launch_bounds__(256) void table_get_kernel(TableGetParams P) {
   int64_t found = -1;
   ItemFields hit{};
   uint64_t hit_off = 0;
-  uint32_t hit_size = 0;
+  uint32_t hit_size = 0, hit_ord = 0;
 
   if (P.lowest_seqno >= snap) outcome = LSM_GET_SEQNO_SKIP;
 
@@ -133,7 +144,8 @@ __global__ __launch_bounds__(256) void table_get_kernel(TableGetParams P) {
           break;
         }
         LoadedBlock d;
-        st = load_block(P, ef.handle_off, ef.val_len, LSM_BLOCK_DATA, d);
+        uint32_t ord = 0;
+        st = load_data_block(P, ef.handle_off, ef.val_len, d, ord);
         if (st == ST_OK) st = point_read_block(d.base, d.p0, d.plen, d.t, nb, np, nn, snap, found, hit);
         if (st != ST_OK) break;
         read_any = true;
@@ -141,6 +153,7 @@ __global__ __launch_bounds__(256) void table_get_kernel(TableGetParams P) {
           outcome = LSM_GET_HIT;
           hit_off = ef.handle_off;
           hit_size = ef.val_len;
+          hit_ord = ord;
           break;
         }
         // the block's end key is above the needle: no later block can hold it
@@ -164,10 +177,36 @@ __global__ __launch_bounds__(256) void table_get_kernel(TableGetParams P) {
     if (P.out.vtype) P.out.vtype[q] = hit.vtype;
     if (P.hit_off) P.hit_off[q] = hit_off;
     if (P.hit_size) P.hit_size[q] = hit_size;
+    if constexpr (Params::kFramed) {
+      if (P.hit_block) P.hit_block[q] = hit_ord;
+    }
   }
 }
 
+__global__ __launch_bounds__(256) void table_get_kernel(TableGetParams P) { table_get_query(P); }
+__global__ __launch_bounds__(256) void table_get_framed_kernel(TableGetFramedParams P) { table_get_query(P); }
+
 }  // namespace lsmgpu
+
+// The arguments both entry points share, checked and laid into P.
+static int table_get_params(const uint8_t* d_file, uint64_t file_len, const lsm_table_scan* table,
+                            uint64_t filter_off, uint32_t filter_size, uint64_t lowest_seqno,
+                            const uint8_t* d_needles, const uint64_t* d_needle_off, const uint64_t* d_snapshot,
+                            const uint64_t* d_key_hash, const uint8_t* d_active, uint32_t n_queries,
+                            const lsm_point_result* d_out, uint64_t* d_hit_block_off, uint32_t* d_hit_block_size,
+                            uint8_t* d_outcome, int32_t* d_status, lsmgpu::TableGetParams& P) {
+  if (!d_file || !table || !d_needles || !d_needle_off || !d_snapshot || !d_out || !d_out->item || !d_status)
+    return LSM_BAD_ARG;
+  // the kernel reads the file and the needles through aligned 4-byte windows from 16-byte-aligned bases
+  if (((uintptr_t)d_file & 15) || ((uintptr_t)d_needles & 15)) return LSM_BAD_ARG;
+  if (table->two_level > 1 || !lsmgpu::tli_in_file(*table, file_len)) return LSM_BAD_ARG;
+  if (filter_size && (filter_off + filter_size < filter_off || filter_off + filter_size > file_len)) return LSM_BAD_ARG;
+  P = lsmgpu::TableGetParams{d_file, file_len, table->tli_off, table->tli_size, table->two_level,
+                             table->global_seqno, filter_off, filter_size, lowest_seqno, d_needles, d_needle_off,
+                             d_snapshot, d_key_hash, d_active, n_queries, *d_out, d_hit_block_off, d_hit_block_size,
+                             d_outcome, d_status};
+  return LSM_OK;
+}
 
 extern "C" int lsm_table_get(const uint8_t* d_file, uint64_t file_len, const lsm_table_scan* table,
                              uint64_t filter_off, uint32_t filter_size, uint64_t lowest_seqno,
@@ -176,15 +215,31 @@ extern "C" int lsm_table_get(const uint8_t* d_file, uint64_t file_len, const lsm
                              const lsm_point_result* d_out, uint64_t* d_hit_block_off, uint32_t* d_hit_block_size,
                              uint8_t* d_outcome, int32_t* d_status, void* stream) {
   if (n_queries == 0) return LSM_OK;
-  if (!d_file || !table || !d_needles || !d_needle_off || !d_snapshot || !d_out || !d_out->item || !d_status)
-    return LSM_BAD_ARG;
-  // the kernel reads the file and the needles through aligned 4-byte windows from 16-byte-aligned bases
-  if (((uintptr_t)d_file & 15) || ((uintptr_t)d_needles & 15)) return LSM_BAD_ARG;
-  if (table->two_level > 1 || !lsmgpu::tli_in_file(*table, file_len)) return LSM_BAD_ARG;
-  if (filter_size && (filter_off + filter_size < filter_off || filter_off + filter_size > file_len)) return LSM_BAD_ARG;
-  lsmgpu::TableGetParams P{d_file, file_len, table->tli_off, table->tli_size, table->two_level, table->global_seqno,
-                           filter_off, filter_size, lowest_seqno, d_needles, d_needle_off, d_snapshot, d_key_hash,
-                           d_active, n_queries, *d_out, d_hit_block_off, d_hit_block_size, d_outcome, d_status};
+  lsmgpu::TableGetParams P;
+  const int rc = table_get_params(d_file, file_len, table, filter_off, filter_size, lowest_seqno, d_needles,
+                                  d_needle_off, d_snapshot, d_key_hash, d_active, n_queries, d_out, d_hit_block_off,
+                                  d_hit_block_size, d_outcome, d_status, P);
+  if (rc != LSM_OK) return rc;
   hipLaunchKernelGGL(lsmgpu::table_get_kernel, dim3((n_queries + 255) / 256), dim3(256), 0, (hipStream_t)stream, P);
   return lsmgpu::hip_status(hipGetLastError(), "lsm_table_get");
+}
+
+extern "C" int lsm_table_get_framed(const uint8_t* d_file, uint64_t file_len, const lsm_table_scan* table,
+                                    uint64_t filter_off, uint32_t filter_size, uint64_t lowest_seqno,
+                                    const uint8_t* d_needles, const uint64_t* d_needle_off,
+                                    const uint64_t* d_snapshot, const uint64_t* d_key_hash, const uint8_t* d_active,
+                                    uint32_t n_queries, const lsm_point_result* d_out, uint64_t* d_hit_block_off,
+                                    uint32_t* d_hit_block_size, uint8_t* d_outcome, int32_t* d_status,
+                                    const void* frames, uint32_t* d_hit_block, void* stream) {
+  if (n_queries == 0) return LSM_OK;
+  lsmgpu::TableGetFramedParams P;
+  const int rc = table_get_params(d_file, file_len, table, filter_off, filter_size, lowest_seqno, d_needles,
+                                  d_needle_off, d_snapshot, d_key_hash, d_active, n_queries, d_out, d_hit_block_off,
+                                  d_hit_block_size, d_outcome, d_status, P);
+  if (rc != LSM_OK) return rc;
+  if (!lsmgpu::frames_view(frames, P.view)) return LSM_BAD_ARG;
+  P.hit_block = d_hit_block;
+  hipLaunchKernelGGL(lsmgpu::table_get_framed_kernel, dim3((n_queries + 255) / 256), dim3(256), 0,
+                     (hipStream_t)stream, P);
+  return lsmgpu::hip_status(hipGetLastError(), "lsm_table_get_framed");
 }

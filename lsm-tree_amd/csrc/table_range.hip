@@ -42,6 +42,7 @@
 namespace lsmgpu {
 
 struct TableRangeParams {
+  static constexpr bool kFramed = false;
   const uint8_t* file;
   uint64_t file_len;
   uint64_t tli_off;
@@ -52,6 +53,24 @@ struct TableRangeParams {
   uint32_t n;
   const uint64_t* data_block_off;
   uint32_t n_data_blocks;
+  lsm_range_result out;
+  uint8_t* outcome;
+  int32_t* status;
+};
+
+// lsm_table_range_framed: the index from the file, every data block from the view's
+// frame of its handle (load_data_block, table_index.hpp), whose ordinal is the block's.
+struct TableRangeFramedParams {
+  static constexpr bool kFramed = true;
+  const uint8_t* file;
+  uint64_t file_len;
+  uint64_t tli_off;
+  uint32_t tli_size;
+  uint32_t two_level;
+  SeekBounds bounds;
+  const uint8_t* flags;
+  uint32_t n;
+  FramesView view;
   lsm_range_result out;
   uint8_t* outcome;
   int32_t* status;
@@ -80,22 +99,25 @@ __device__ __forceinline__ int32_t index_span(const LoadedBlock& blk, const Seek
 }
 
 // The data block of index entry e of part: loaded and seeked with both bounds.
-__device__ __forceinline__ int32_t range_in_block(const TableRangeParams& P, const LoadedBlock& part, uint32_t e,
-                                                  uint32_t q, uint32_t fl, uint64_t& off, uint32_t& size,
+// ord: its ordinal in the view (framed only).
+template <class Params>
+__device__ __forceinline__ int32_t range_in_block(const Params& P, const LoadedBlock& part, uint32_t e, uint32_t q,
+                                                  uint32_t fl, uint64_t& off, uint32_t& size, uint32_t& ord,
                                                   uint32_t& first, uint32_t& end) {
   ItemFields ef;
   if (!index_entry(part, e, ef)) return ST_PARSE;
   off = ef.handle_off;
   size = ef.val_len;
   LoadedBlock d;
-  const int32_t st = load_block(P, off, size, LSM_BLOCK_DATA, d);
+  const int32_t st = load_data_block(P, off, size, d, ord);
   if (st != ST_OK) return st;
   uint32_t found = 0;
   return seek_block(d.base, d.p0, d.t, P.bounds, q, fl, first, end, found);
 }
 
 // Partition pi of a two-level index: loaded and spanned.
-__device__ __forceinline__ int32_t load_partition(const TableRangeParams& P, const LoadedBlock& tli, uint32_t pi,
+template <class Params>
+__device__ __forceinline__ int32_t load_partition(const Params& P, const LoadedBlock& tli, uint32_t pi,
                                                   uint32_t q, uint32_t fl, LoadedBlock& part, uint32_t& a,
                                                   uint32_t& b, bool& none) {
   ItemFields pf;
@@ -119,7 +141,9 @@ __device__ __forceinline__ bool block_ordinal(const uint64_t* off, uint32_t n, u
   return true;
 }
 
-__global__ __launch_bounds__(256) void table_range_kernel(TableRangeParams P) {
+// The body of both kernels (the plain one compiles to the code it had as a kernel of its own).
+template <class Params>
+__device__ __forceinline__ void table_range_query(const Params& P) {
   const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= P.n) return;
   const uint32_t fl = P.flags[q];
@@ -127,6 +151,7 @@ __global__ __launch_bounds__(256) void table_range_kernel(TableRangeParams P) {
   uint32_t outcome = LSM_RANGE_NO_BLOCK;
   uint64_t f_off = 0, l_off = 0;
   uint32_t f_size = 0, f_first = 0, f_end = 0, l_size = 0, l_item = 0;
+  uint32_t f_ord = 0, l_ord = 0;  // (framed: the loads give them; plain: searched at the end)
 
   // 1. the TLI; the partitions ta..=tb to visit (the TLI itself under a full index)
   LoadedBlock tli;
@@ -146,7 +171,7 @@ __global__ __launch_bounds__(256) void table_range_kernel(TableRangeParams P) {
                        : index_span(part, P.bounds, q, fl, pa, pb, none);
       if (st != ST_OK || none) break;  // a lower seek that finds nothing ends the drain
       for (fe = pa; fe <= pb; ++fe) {
-        st = range_in_block(P, part, fe, q, fl, f_off, f_size, f_first, f_end);
+        st = range_in_block(P, part, fe, q, fl, f_off, f_size, f_ord, f_first, f_end);
         if (st != ST_OK) break;
         outcome = LSM_RANGE_EMPTY;
         if (f_first < f_end) {
@@ -164,6 +189,7 @@ __global__ __launch_bounds__(256) void table_range_kernel(TableRangeParams P) {
     const uint32_t fpi = cur;
     l_off = f_off;
     l_size = f_size;
+    l_ord = f_ord;
     l_item = f_end - 1;
     bool got = false;
     for (uint32_t pi = tb;; --pi) {
@@ -176,12 +202,13 @@ __global__ __launch_bounds__(256) void table_range_kernel(TableRangeParams P) {
       for (uint32_t e = none ? stop : pb + 1; e > stop;) {
         --e;
         uint64_t off;
-        uint32_t size, first, end;
-        st = range_in_block(P, part, e, q, fl, off, size, first, end);
+        uint32_t size, ord = 0, first, end;
+        st = range_in_block(P, part, e, q, fl, off, size, ord, first, end);
         if (st != ST_OK) break;
         if (first < end) {
           l_off = off;
           l_size = size;
+          l_ord = ord;
           l_item = end - 1;
           got = true;
           break;
@@ -192,11 +219,14 @@ __global__ __launch_bounds__(256) void table_range_kernel(TableRangeParams P) {
   }
 
   // the two blocks' ordinals in the caller's data-block offsets
-  uint32_t f_ord = 0, l_ord = 0;
-  if (st == ST_OK && outcome == LSM_RANGE_ROWS && P.data_block_off) {
-    if (!block_ordinal(P.data_block_off, P.n_data_blocks, f_off, f_size, f_ord) ||
-        !block_ordinal(P.data_block_off, P.n_data_blocks, l_off, l_size, l_ord))
-      st = ST_BAD_ARG;  // not this table's offsets
+  bool ordinals = true;
+  if constexpr (!Params::kFramed) {
+    ordinals = P.data_block_off != nullptr;
+    if (st == ST_OK && outcome == LSM_RANGE_ROWS && ordinals) {
+      if (!block_ordinal(P.data_block_off, P.n_data_blocks, f_off, f_size, f_ord) ||
+          !block_ordinal(P.data_block_off, P.n_data_blocks, l_off, l_size, l_ord))
+        st = ST_BAD_ARG;  // not this table's offsets
+    }
   }
 
   P.status[q] = st;
@@ -208,12 +238,15 @@ __global__ __launch_bounds__(256) void table_range_kernel(TableRangeParams P) {
     if (P.out.last_block_off) P.out.last_block_off[q] = l_off;
     if (P.out.last_block_size) P.out.last_block_size[q] = l_size;
     P.out.last_item[q] = l_item;
-    if (P.data_block_off) {
+    if (ordinals) {
       if (P.out.first_block) P.out.first_block[q] = f_ord;
       if (P.out.last_block) P.out.last_block[q] = l_ord;
     }
   }
 }
+
+__global__ __launch_bounds__(256) void table_range_kernel(TableRangeParams P) { table_range_query(P); }
+__global__ __launch_bounds__(256) void table_range_framed_kernel(TableRangeFramedParams P) { table_range_query(P); }
 
 }  // namespace lsmgpu
 
@@ -237,4 +270,26 @@ extern "C" int lsm_table_range(const uint8_t* d_file, uint64_t file_len, const l
   hipLaunchKernelGGL(lsmgpu::table_range_kernel, dim3((n_queries + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                      P);
   return lsmgpu::hip_status(hipGetLastError(), "lsm_table_range");
+}
+
+extern "C" int lsm_table_range_framed(const uint8_t* d_file, uint64_t file_len, const lsm_table_scan* table,
+                                      const uint8_t* d_lo, const uint64_t* d_lo_off, const uint8_t* d_hi,
+                                      const uint64_t* d_hi_off, const uint8_t* d_flags, uint32_t n_queries,
+                                      const void* frames, const void* d_out, uint8_t* d_outcome, int32_t* d_status,
+                                      void* stream) {
+  if (n_queries == 0) return LSM_OK;
+  const lsm_range_result* out = static_cast<const lsm_range_result*>(d_out);
+  if (!d_file || !table || !d_lo || !d_lo_off || !d_hi || !d_hi_off || !d_flags || !out || !out->first_item ||
+      !out->last_item || !d_outcome || !d_status)
+    return LSM_BAD_ARG;
+  if (((uintptr_t)d_file & 15) || ((uintptr_t)d_lo & 15) || ((uintptr_t)d_hi & 15)) return LSM_BAD_ARG;
+  if (table->two_level > 1 || !lsmgpu::tli_in_file(*table, file_len)) return LSM_BAD_ARG;
+  lsmgpu::FramesView view;
+  if (!lsmgpu::frames_view(frames, view)) return LSM_BAD_ARG;
+  lsmgpu::TableRangeFramedParams P{d_file, file_len, table->tli_off, table->tli_size, table->two_level,
+                                   lsmgpu::SeekBounds{d_lo, d_lo_off, d_hi, d_hi_off}, d_flags, n_queries, view,
+                                   *out, d_outcome, d_status};
+  hipLaunchKernelGGL(lsmgpu::table_range_framed_kernel, dim3((n_queries + 255) / 256), dim3(256), 0,
+                     (hipStream_t)stream, P);
+  return lsmgpu::hip_status(hipGetLastError(), "lsm_table_range_framed");
 }

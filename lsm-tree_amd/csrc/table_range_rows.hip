@@ -72,6 +72,7 @@ static_assert(sizeof(RrDesc) == 32, "descriptor size");
 enum { kRrBase = 0, kRrRows = 3, kRrPairs = 4, kRrOverflow = 5, kRrMeta = 8 };
 
 struct RrParams {
+  static constexpr bool kFramed = false;
   const uint8_t* file;
   uint64_t file_len;
   uint64_t global_seqno;
@@ -108,6 +109,14 @@ struct RrParams {
   uint64_t* out_seqno;
   uint8_t* out_vtype;
   uint64_t item_cap, key_cap, val_cap;
+};
+
+// The framed calls: file / file_len / off are the view's frame arena, its length and
+// frame_off, so block b is frame b and the kernels that load no block (pairs, fold,
+// finish, gather) are the plain ones; the two that do take the frames' statuses too.
+struct RrFramedParams : RrParams {
+  static constexpr bool kFramed = true;
+  const int32_t* frame_status;  // [n_blocks] or null
 };
 
 // ---------------------------------------------------------------- group helpers
@@ -177,8 +186,16 @@ __device__ __forceinline__ bool rr_in_window(const RrPair& x, uint32_t k) {
 
 // Block b of the offsets, loaded as a data block: the handle test (a handle
 // shorter than a header, one that decreases, one ending past the file), then
-// load_block's checks in its order.
-__device__ __forceinline__ int32_t rr_load(const RrParams& P, uint32_t b, LoadedBlock& blk, uint64_t& o0) {
+// load_block's checks in its order.  Framed: the frame's status before them
+// (load_frame, table_index.hpp); one that the fault word's byte cannot carry
+// (not a status of this library) counts as LSM_BAD_ARG.
+template <class Params>
+__device__ __forceinline__ int32_t rr_load(const Params& P, uint32_t b, LoadedBlock& blk, uint64_t& o0) {
+  if constexpr (Params::kFramed) {
+    const int32_t st =
+        load_frame(FramesView{nullptr, P.file, P.off, P.frame_status, P.file_len, P.n_blocks}, b, blk, o0);
+    return st < 0 || st > 0xFF ? (int32_t)ST_BAD_ARG : st;
+  }
   o0 = P.off[b];
   const uint64_t o1 = P.off[b + 1];
   if (o1 < o0 || o1 - o0 < kHdrLen || o1 > P.file_len) return ST_TRUNCATED;
@@ -255,7 +272,10 @@ struct RrPrefixOut {
   __device__ void operator()(uint64_t i, uint64_t prefix) const { dst[i] = prefix; }
 };
 
-__global__ __launch_bounds__(kRrThreads) void rr_measure_kernel(RrParams P) {
+// The bodies of rr_measure_kernel / rr_rows_kernel and of their framed twins (the
+// plain ones compile to the code they had as kernels of their own).
+template <class Params>
+__device__ __forceinline__ void rr_measure(const Params& P) {
   const uint32_t gl = threadIdx.x & (kRrGroup - 1);
   const uint64_t p = (uint64_t)blockIdx.x * kRrGroupsPerWg + threadIdx.x / kRrGroup;
   const uint64_t np = P.pair_start[P.n];
@@ -291,6 +311,9 @@ __global__ __launch_bounds__(kRrThreads) void rr_measure_kernel(RrParams P) {
     if (st != ST_OK) atomicMin((unsigned long long*)&P.fault[x.q], ((unsigned long long)x.b << 8) | (uint32_t)st);
   }
 }
+
+__global__ __launch_bounds__(kRrThreads) void rr_measure_kernel(RrParams P) { rr_measure(P); }
+__global__ __launch_bounds__(kRrThreads) void rr_measure_framed_kernel(RrFramedParams P) { rr_measure(P); }
 
 __global__ __launch_bounds__(256) void rr_fold_kernel(RrParams P) {
   const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -349,7 +372,8 @@ __device__ __forceinline__ bool rr_fits(const RrParams& P) {
          P.end[1] <= P.key_cap && P.end[2] <= P.val_cap && P.meta[kRrBase + 0] + P.meta[kRrRows] == P.end[0];
 }
 
-__global__ __launch_bounds__(kRrThreads) void rr_rows_kernel(RrParams P) {
+template <class Params>
+__device__ __forceinline__ void rr_rows(const Params& P) {
   const uint32_t gl = threadIdx.x & (kRrGroup - 1);
   const uint64_t p = (uint64_t)blockIdx.x * kRrGroupsPerWg + threadIdx.x / kRrGroup;
   const bool fits = rr_fits(P);
@@ -413,6 +437,9 @@ __global__ __launch_bounds__(kRrThreads) void rr_rows_kernel(RrParams P) {
     v0 += rr_shfl(vi, kRrGroup - 1);
   }
 }
+
+__global__ __launch_bounds__(kRrThreads) void rr_rows_kernel(RrParams P) { rr_rows(P); }
+__global__ __launch_bounds__(kRrThreads) void rr_rows_framed_kernel(RrFramedParams P) { rr_rows(P); }
 
 // The gather's row source: the descriptors of the rows pass (items_gather.hpp).
 // A descriptor that does not lie in the file names no bytes (the rows pass
@@ -517,6 +544,63 @@ static int rr_params(const uint8_t* d_file, uint64_t file_len, const lsm_table_s
 
 static uint32_t rr_grid(uint64_t n, uint32_t per_wg) { return (uint32_t)((n + per_wg - 1) / per_wg); }
 
+// The view's arrays in the places of the file and the offsets (RrFramedParams).
+static int rr_framed_params(const lsm_table_scan* table, const void* frames, const void* pos, uint32_t n_queries,
+                            uint64_t block_cap, uint64_t row_cap, const uint64_t* d_base, const uint64_t* d_end,
+                            void* d_workspace, size_t workspace_bytes, RrFramedParams& P) {
+  FramesView V;
+  if (!frames_view(frames, V)) return LSM_BAD_ARG;
+  const int rc = rr_params(V.frames, V.frames_len, table, V.frame_off, V.n_blocks, pos, n_queries, block_cap,
+                           row_cap, d_base, d_end, d_workspace, workspace_bytes, P);
+  P.frame_status = V.frame_status;
+  return rc;
+}
+
+// n_queries == 0: the cursor does not move.
+static int rr_plan_empty(const uint64_t* d_base, uint64_t* d_run_start, uint64_t* d_end, uint64_t* d_need,
+                         int32_t* d_result, hipStream_t st, const char* what) {
+  if (!d_end || !d_result || d_end == d_base) return LSM_BAD_ARG;
+  RrParams P{};
+  P.base = d_base;
+  P.end = d_end;
+  P.run_start = d_run_start;
+  P.need = d_need;
+  P.result = d_result;
+  hipLaunchKernelGGL(rr_finish_kernel, dim3(1), dim3(256), 0, st, P, true);
+  return hip_status(hipGetLastError(), what);
+}
+
+// The plan's launches over checked params (RrParams or RrFramedParams).
+template <class Params>
+static int rr_plan(Params& P, uint32_t n_queries, uint64_t block_cap, uint64_t* d_run_start, uint64_t* d_need,
+                   int32_t* d_row_status, int32_t* d_result, hipStream_t st, const char* what) {
+  if (!d_run_start || !d_need || !d_row_status || !d_result) return LSM_BAD_ARG;
+  P.run_start = d_run_start;
+  P.need = d_need;
+  P.row_status = d_row_status;
+  P.result = d_result;
+  const RrParams& base = P;
+  hipLaunchKernelGGL(rr_pairs_kernel, dim3(rr_grid(n_queries, 256)), dim3(256), 0, st, base);
+  hipError_t e = launch_excl_scan(P.qpairs, (uint64_t)n_queries, P.tiles, RrPrefixOut{P.pair_start}, st);
+  if (e != hipSuccess) return hip_status(e, what);
+  if (block_cap) {
+    const dim3 grid(rr_grid(block_cap, kRrGroupsPerWg));
+    if constexpr (Params::kFramed) hipLaunchKernelGGL(rr_measure_framed_kernel, grid, dim3(kRrThreads), 0, st, P);
+    else hipLaunchKernelGGL(rr_measure_kernel, grid, dim3(kRrThreads), 0, st, P);
+    hipLaunchKernelGGL(rr_fold_kernel, dim3(rr_grid(block_cap, 256)), dim3(256), 0, st, base);
+    const struct {
+      const uint64_t* in;
+      uint64_t* out;
+    } cols[3] = {{P.prow, P.srow}, {P.pkey, P.skey}, {P.pval, P.sval}};
+    for (const auto& c : cols) {
+      e = launch_excl_scan(c.in, block_cap, P.tiles, RrPrefixOut{c.out}, st);
+      if (e != hipSuccess) return hip_status(e, what);
+    }
+  }
+  hipLaunchKernelGGL(rr_finish_kernel, dim3(rr_grid((uint64_t)n_queries + 1, 256)), dim3(256), 0, st, base, false);
+  return hip_status(hipGetLastError(), what);
+}
+
 extern "C" int lsm_table_range_rows_plan(const uint8_t* d_file, uint64_t file_len, const lsm_table_scan* table,
                                          const uint64_t* d_data_block_off, uint32_t n_data_blocks, const void* pos,
                                          uint32_t n_queries, uint64_t block_cap, uint64_t row_cap,
@@ -524,64 +608,45 @@ extern "C" int lsm_table_range_rows_plan(const uint8_t* d_file, uint64_t file_le
                                          uint64_t* d_need, int32_t* d_row_status, int32_t* d_result,
                                          void* d_workspace, size_t workspace_bytes, void* stream) {
   const hipStream_t st = (hipStream_t)stream;
-  if (n_queries == 0) {  // the cursor does not move
-    if (!d_end || !d_result || d_end == d_base) return LSM_BAD_ARG;
-    RrParams P{};
-    P.base = d_base;
-    P.end = d_end;
-    P.run_start = d_run_start;
-    P.need = d_need;
-    P.result = d_result;
-    hipLaunchKernelGGL(rr_finish_kernel, dim3(1), dim3(256), 0, st, P, true);
-    return hip_status(hipGetLastError(), "lsm_table_range_rows_plan");
-  }
+  const char* what = "lsm_table_range_rows_plan";
+  if (n_queries == 0) return rr_plan_empty(d_base, d_run_start, d_end, d_need, d_result, st, what);
   RrParams P;
   const int rc = rr_params(d_file, file_len, table, d_data_block_off, n_data_blocks, pos, n_queries, block_cap,
                            row_cap, d_base, d_end, d_workspace, workspace_bytes, P);
   if (rc != LSM_OK) return rc;
-  if (!d_run_start || !d_need || !d_row_status || !d_result) return LSM_BAD_ARG;
-  P.run_start = d_run_start;
-  P.need = d_need;
-  P.row_status = d_row_status;
-  P.result = d_result;
-  hipLaunchKernelGGL(rr_pairs_kernel, dim3(rr_grid(n_queries, 256)), dim3(256), 0, st, P);
-  hipError_t e = launch_excl_scan(P.qpairs, (uint64_t)n_queries, P.tiles, RrPrefixOut{P.pair_start}, st);
-  if (e != hipSuccess) return hip_status(e, "lsm_table_range_rows_plan");
-  if (block_cap) {
-    hipLaunchKernelGGL(rr_measure_kernel, dim3(rr_grid(block_cap, kRrGroupsPerWg)), dim3(kRrThreads), 0, st, P);
-    hipLaunchKernelGGL(rr_fold_kernel, dim3(rr_grid(block_cap, 256)), dim3(256), 0, st, P);
-    const struct {
-      const uint64_t* in;
-      uint64_t* out;
-    } cols[3] = {{P.prow, P.srow}, {P.pkey, P.skey}, {P.pval, P.sval}};
-    for (const auto& c : cols) {
-      e = launch_excl_scan(c.in, block_cap, P.tiles, RrPrefixOut{c.out}, st);
-      if (e != hipSuccess) return hip_status(e, "lsm_table_range_rows_plan");
-    }
-  }
-  hipLaunchKernelGGL(rr_finish_kernel, dim3(rr_grid((uint64_t)n_queries + 1, 256)), dim3(256), 0, st, P, false);
-  return hip_status(hipGetLastError(), "lsm_table_range_rows_plan");
+  return rr_plan(P, n_queries, block_cap, d_run_start, d_need, d_row_status, d_result, st, what);
+}
+
+extern "C" int lsm_table_range_rows_plan_framed(const lsm_table_scan* table, const void* frames, const void* pos,
+                                                uint32_t n_queries, uint64_t block_cap, uint64_t row_cap,
+                                                const uint64_t* d_base, uint64_t* d_run_start, uint64_t* d_end,
+                                                uint64_t* d_need, int32_t* d_row_status, int32_t* d_result,
+                                                void* d_workspace, size_t workspace_bytes, void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
+  const char* what = "lsm_table_range_rows_plan_framed";
+  if (n_queries == 0) return rr_plan_empty(d_base, d_run_start, d_end, d_need, d_result, st, what);
+  RrFramedParams P;
+  const int rc = rr_framed_params(table, frames, pos, n_queries, block_cap, row_cap, d_base, d_end, d_workspace,
+                                  workspace_bytes, P);
+  if (rc != LSM_OK) return rc;
+  return rr_plan(P, n_queries, block_cap, d_run_start, d_need, d_row_status, d_result, st, what);
 }
 
 __global__ void rr_result_kernel(int32_t* result) { *result = LSM_OK; }
 
-extern "C" int lsm_table_range_rows(const uint8_t* d_file, uint64_t file_len, const lsm_table_scan* table,
-                                    const uint64_t* d_data_block_off, uint32_t n_data_blocks, const void* pos,
-                                    uint32_t n_queries, uint64_t block_cap, uint64_t row_cap, const uint64_t* d_base,
-                                    const uint64_t* d_end, void* d_workspace, size_t workspace_bytes,
-                                    uint64_t* d_out_key_off, uint64_t* d_out_val_off, uint8_t* d_out_keys,
-                                    uint64_t key_cap, uint8_t* d_out_vals, uint64_t val_cap, uint64_t* d_out_seqno,
-                                    uint8_t* d_out_vtype, uint64_t out_item_cap, int32_t* d_result, void* stream) {
-  const hipStream_t st = (hipStream_t)stream;
-  if (n_queries == 0) {
-    if (!d_result) return LSM_BAD_ARG;
-    hipLaunchKernelGGL(rr_result_kernel, dim3(1), dim3(1), 0, st, d_result);
-    return hip_status(hipGetLastError(), "lsm_table_range_rows");
-  }
-  RrParams P;
-  const int rc = rr_params(d_file, file_len, table, d_data_block_off, n_data_blocks, pos, n_queries, block_cap,
-                           row_cap, d_base, d_end, d_workspace, workspace_bytes, P);
-  if (rc != LSM_OK) return rc;
+// n_queries == 0: nothing to write but the result.
+static int rr_rows_empty(int32_t* d_result, hipStream_t st, const char* what) {
+  if (!d_result) return LSM_BAD_ARG;
+  hipLaunchKernelGGL(rr_result_kernel, dim3(1), dim3(1), 0, st, d_result);
+  return hip_status(hipGetLastError(), what);
+}
+
+// The rows call's launches over checked params (RrParams or RrFramedParams).
+template <class Params>
+static int rr_rows_call(Params& P, uint64_t block_cap, uint64_t row_cap, uint64_t* d_out_key_off,
+                        uint64_t* d_out_val_off, uint8_t* d_out_keys, uint64_t key_cap, uint8_t* d_out_vals,
+                        uint64_t val_cap, uint64_t* d_out_seqno, uint8_t* d_out_vtype, uint64_t out_item_cap,
+                        int32_t* d_result, hipStream_t st, const char* what) {
   if (!d_out_key_off || !d_out_val_off || !d_out_keys || !d_out_vals || !d_out_seqno || !d_out_vtype || !d_result)
     return LSM_BAD_ARG;
   P.out_key_off = d_out_key_off;
@@ -595,9 +660,48 @@ extern "C" int lsm_table_range_rows(const uint8_t* d_file, uint64_t file_len, co
   P.val_cap = val_cap;
   P.result = d_result;
   // (block_cap == 0: one workgroup still reports the result and writes the closing offsets)
-  hipLaunchKernelGGL(rr_rows_kernel, dim3(rr_grid(block_cap ? block_cap : 1, kRrGroupsPerWg)), dim3(kRrThreads), 0,
-                     st, P);
-  if (row_cap)
-    hipLaunchKernelGGL(rr_gather_kernel, dim3(rr_grid(row_cap, kMiWaves * 64)), dim3(kMiWaves * 64), 0, st, P);
-  return hip_status(hipGetLastError(), "lsm_table_range_rows");
+  const dim3 grid(rr_grid(block_cap ? block_cap : 1, kRrGroupsPerWg));
+  if constexpr (Params::kFramed) hipLaunchKernelGGL(rr_rows_framed_kernel, grid, dim3(kRrThreads), 0, st, P);
+  else hipLaunchKernelGGL(rr_rows_kernel, grid, dim3(kRrThreads), 0, st, P);
+  if (row_cap) {
+    const RrParams& base = P;
+    hipLaunchKernelGGL(rr_gather_kernel, dim3(rr_grid(row_cap, kMiWaves * 64)), dim3(kMiWaves * 64), 0, st, base);
+  }
+  return hip_status(hipGetLastError(), what);
+}
+
+extern "C" int lsm_table_range_rows(const uint8_t* d_file, uint64_t file_len, const lsm_table_scan* table,
+                                    const uint64_t* d_data_block_off, uint32_t n_data_blocks, const void* pos,
+                                    uint32_t n_queries, uint64_t block_cap, uint64_t row_cap, const uint64_t* d_base,
+                                    const uint64_t* d_end, void* d_workspace, size_t workspace_bytes,
+                                    uint64_t* d_out_key_off, uint64_t* d_out_val_off, uint8_t* d_out_keys,
+                                    uint64_t key_cap, uint8_t* d_out_vals, uint64_t val_cap, uint64_t* d_out_seqno,
+                                    uint8_t* d_out_vtype, uint64_t out_item_cap, int32_t* d_result, void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
+  const char* what = "lsm_table_range_rows";
+  if (n_queries == 0) return rr_rows_empty(d_result, st, what);
+  RrParams P;
+  const int rc = rr_params(d_file, file_len, table, d_data_block_off, n_data_blocks, pos, n_queries, block_cap,
+                           row_cap, d_base, d_end, d_workspace, workspace_bytes, P);
+  if (rc != LSM_OK) return rc;
+  return rr_rows_call(P, block_cap, row_cap, d_out_key_off, d_out_val_off, d_out_keys, key_cap, d_out_vals, val_cap,
+                      d_out_seqno, d_out_vtype, out_item_cap, d_result, st, what);
+}
+
+extern "C" int lsm_table_range_rows_framed(const lsm_table_scan* table, const void* frames, const void* pos,
+                                           uint32_t n_queries, uint64_t block_cap, uint64_t row_cap,
+                                           const uint64_t* d_base, const uint64_t* d_end, void* d_workspace,
+                                           size_t workspace_bytes, uint64_t* d_out_key_off, uint64_t* d_out_val_off,
+                                           uint8_t* d_out_keys, uint64_t key_cap, uint8_t* d_out_vals,
+                                           uint64_t val_cap, uint64_t* d_out_seqno, uint8_t* d_out_vtype,
+                                           uint64_t out_item_cap, int32_t* d_result, void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
+  const char* what = "lsm_table_range_rows_framed";
+  if (n_queries == 0) return rr_rows_empty(d_result, st, what);
+  RrFramedParams P;
+  const int rc = rr_framed_params(table, frames, pos, n_queries, block_cap, row_cap, d_base, d_end, d_workspace,
+                                  workspace_bytes, P);
+  if (rc != LSM_OK) return rc;
+  return rr_rows_call(P, block_cap, row_cap, d_out_key_off, d_out_val_off, d_out_keys, key_cap, d_out_vals, val_cap,
+                      d_out_seqno, d_out_vtype, out_item_cap, d_result, st, what);
 }

@@ -87,6 +87,11 @@ class LsmRangePositions(C.Structure):  # lsm_range_positions: lsm_table_range's 
                 ("first_item", C.c_void_p), ("last_block", C.c_void_p), ("last_item", C.c_void_p)]
 
 
+class LsmTableFrames(C.Structure):  # lsm_table_frames: a table's data blocks as inflated frames (table_frames)
+    _fields_ = [("stored_off", C.c_void_p), ("frames", C.c_void_p), ("frame_off", C.c_void_p),
+                ("frame_status", C.c_void_p), ("frames_len", C.c_uint64), ("n_blocks", C.c_uint32)]
+
+
 ABI_VERSION = 7
 DECODE_ITEM_START_VALID = 1
 # lsm_decode_tuning.flags / lsm_block_params.flags: take the workspace pool (explicit opt-in)
@@ -456,8 +461,15 @@ TABLE_GET_FIELDS = (("item", "int32"), ("seqno", "int64"), ("val_off", "int32"),
                     ("status", "int32"))
 
 
+def _frames_struct(frames):
+    """The lsm_table_frames of a view dict (table_frames' result, or one built by hand: stored_off,
+    frames, frame_off, n_blocks, frames_len and an optional status)."""
+    return LsmTableFrames(_ptr(frames["stored_off"]), _ptr(frames["frames"]), _ptr(frames["frame_off"]),
+                          _ptr(frames.get("status")), int(frames["frames_len"]), int(frames["n_blocks"]))
+
+
 def table_get(file, table, needles, needle_off, snapshot, key_hash=None, active=None, filter=None, lowest_seqno=0,
-              global_seqno=0, stream=None, out=None):
+              global_seqno=0, stream=None, out=None, frames=None):
     """Batched Table::get (src/table/mod.rs:229-340) on a table file image: file = padded uint8
     cuda tensor; table = dict with tli_off, tli_size, two_level (write_table's result with
     two_level added; an optional file_len, else the end of the TLI / filter region); needles uint8
@@ -467,6 +479,9 @@ def table_get(file, table, needles, needle_off, snapshot, key_hash=None, active=
     (GET_*)/status; item -1 = no hit, the value of a hit is
     file[block_off + 33 + val_off : ... + val_len].  out: such a dict to write into (rows of
     inactive queries keep what it holds), e.g. the result of the previous, newer table.
+    frames: table_frames' view of an LZ4 table (lsm_table_get_framed): block_off / block_size are
+    the stored handle, the result gains block (int32: the handle's ordinal in frames["stored_off"])
+    and the value of a hit is frames["frames"][frame_off[block] + 33 + val_off : ... + val_len].
     No host synchronisation."""
     torch = _torch()
     n = int(snapshot.numel())
@@ -476,10 +491,17 @@ def table_get(file, table, needles, needle_off, snapshot, key_hash=None, active=
     f_off, f_size = filter if filter is not None else (0, 0)
     t = _table_struct(table, global_seqno)
     res = _point_result(out)
-    _check(lib().lsm_table_get(_ptr(file), _file_len(table, f_off + f_size), C.byref(t), f_off, f_size, lowest_seqno,
-                               _ptr(needles), _ptr(needle_off), _ptr(snapshot), _ptr(key_hash), _ptr(active), n,
-                               C.byref(res), _ptr(out["block_off"]), _ptr(out["block_size"]), _ptr(out["outcome"]),
-                               _ptr(out["status"]), _stream(stream)), "lsm_table_get")
+    args = (_ptr(file), _file_len(table, f_off + f_size), C.byref(t), f_off, f_size, lowest_seqno, _ptr(needles),
+            _ptr(needle_off), _ptr(snapshot), _ptr(key_hash), _ptr(active), n, C.byref(res), _ptr(out["block_off"]),
+            _ptr(out["block_size"]), _ptr(out["outcome"]), _ptr(out["status"]))
+    if frames is None:
+        _check(lib().lsm_table_get(*args, _stream(stream)), "lsm_table_get")
+        return out
+    if "block" not in out:
+        out["block"] = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    view = _frames_struct(frames)
+    _check(lib().lsm_table_get_framed(*args, C.byref(view), _ptr(out["block"]), _stream(stream)),
+           "lsm_table_get_framed")
     return out
 
 
@@ -491,7 +513,7 @@ TABLE_RANGE_FIELDS = (("first_block_off", "int64"), ("first_block_size", "int32"
                       ("first_block", "int32"), ("last_block", "int32"), ("outcome", "uint8"), ("status", "int32"))
 
 
-def table_range(file, table, lo, lo_off, hi, hi_off, flags, scan=None, out=None, stream=None):
+def table_range(file, table, lo, lo_off, hi, hi_off, flags, scan=None, out=None, stream=None, frames=None):
     """Batched Table::range bounds (src/table/mod.rs:391-422, the forward drain of
     src/table/iter.rs:94-293) on a table file image: file = padded uint8 cuda tensor; table = dict
     with tli_off, tli_size, two_level (and an optional file_len, else the end of the TLI); lo / hi
@@ -504,6 +526,9 @@ def table_range(file, table, lo, lo_off, hi, hi_off, flags, scan=None, out=None,
     as scan_table returns: first_block / last_block are then the two blocks' ordinals, and
     row_first / row_end the row window [item_start[first_block] + first_item,
     item_start[last_block] + last_item + 1) of the scan, 0 / 0 where the outcome is not RANGE_ROWS.
+    frames: table_frames' view of an LZ4 table (lsm_table_range_framed): the handles are the stored
+    ones, first_block / last_block their ordinals in frames["stored_off"] (scan's block_off is not
+    read; its item_start still gives the row window), the items index the decompressed blocks.
     No host synchronisation."""
     torch = _torch()
     n = int(flags.numel())
@@ -516,11 +541,15 @@ def table_range(file, table, lo, lo_off, hi, hi_off, flags, scan=None, out=None,
         block_off = scan["block_off"]
         nb = scan.get("n_blocks")
         n_blocks = nb if isinstance(nb, int) else int(block_off.numel()) - 1
-    res = LsmRangeResult(*(_ptr(out[f]) if block_off is not None or not f.endswith("_block") else None
-                           for f, _ in TABLE_RANGE_FIELDS[:8]))
-    _check(lib().lsm_table_range(_ptr(file), _file_len(table), C.byref(t), _ptr(lo), _ptr(lo_off), _ptr(hi),
-                                 _ptr(hi_off), _ptr(flags), n, _ptr(block_off), n_blocks, C.byref(res),
-                                 _ptr(out["outcome"]), _ptr(out["status"]), _stream(stream)), "lsm_table_range")
+    res = LsmRangeResult(*(_ptr(out[f]) if block_off is not None or frames is not None or not f.endswith("_block")
+                           else None for f, _ in TABLE_RANGE_FIELDS[:8]))
+    head = (_ptr(file), _file_len(table), C.byref(t), _ptr(lo), _ptr(lo_off), _ptr(hi), _ptr(hi_off), _ptr(flags), n)
+    tail = (C.byref(res), _ptr(out["outcome"]), _ptr(out["status"]), _stream(stream))
+    if frames is None:
+        _check(lib().lsm_table_range(*head, _ptr(block_off), n_blocks, *tail), "lsm_table_range")
+    else:
+        view = _frames_struct(frames)
+        _check(lib().lsm_table_range_framed(*head, C.byref(view), *tail), "lsm_table_range_framed")
     if scan is not None:
         rows = out["outcome"][:n] == RANGE_ROWS
         start = scan["item_start"].to(torch.int64)
@@ -586,7 +615,7 @@ RANGE_ROWS_AUTO_PAIRS = 1 << 22
 
 
 def table_range_rows(file, table, positions, block_off, base=None, into=None, caps=None, stream=None,
-                     n_queries=None):
+                     n_queries=None, frames=None):
     """lsm_table_range_rows_plan + lsm_table_range_rows: the rows between the positions of
     table_range, as item runs.  file / table as table_range (table["global_seqno"], default 0, is
     added to every seqno); positions: the dict table_range(..., scan={"block_off": block_off})
@@ -606,17 +635,27 @@ def table_range_rows(file, table, positions, block_off, base=None, into=None, ca
     caps=None: a sizing plan with row_cap 0 and block_cap n_queries x n_blocks runs first and
     need is read back once, the only host synchronisation (above RANGE_ROWS_AUTO_PAIRS possible
     pairs the pair count is read back first, by itself); without `into` the outputs are
-    allocated for need and trimmed to the rows."""
+    allocated for need and trimmed to the rows.
+    frames: table_frames' view of an LZ4 table (lsm_table_range_rows_plan_framed /
+    lsm_table_range_rows_framed): block b is frame b, positions are table_range(..., frames=frames)'s;
+    file and block_off are not read (block_off may be None)."""
     torch = _torch()
     dev = file.device
     n = int(positions["outcome"].numel()) if n_queries is None else int(n_queries)
-    n_blocks = int(block_off.numel()) - 1
     t = _table_struct(table, table.get("global_seqno", 0))
     ps = LsmRangePositions(*(_ptr(positions[f]) for f, _ in LsmRangePositions._fields_))
     if base is not None and into is None:
         raise LsmError("table_range_rows: a base needs `into` (the outputs it already fills)")
     st = _stream(stream)
-    head = (_ptr(file), _file_len(table), C.byref(t), _ptr(block_off), n_blocks, C.byref(ps), n)  # both calls'
+    if frames is None:
+        n_blocks = int(block_off.numel()) - 1
+        plan_fn, rows_fn = "lsm_table_range_rows_plan", "lsm_table_range_rows"
+        head = (_ptr(file), _file_len(table), C.byref(t), _ptr(block_off), n_blocks, C.byref(ps), n)  # both calls'
+    else:
+        n_blocks = int(frames["n_blocks"])
+        view = _frames_struct(frames)
+        plan_fn, rows_fn = "lsm_table_range_rows_plan_framed", "lsm_table_range_rows_framed"
+        head = (C.byref(t), C.byref(view), C.byref(ps), n)
     run_start = torch.zeros(n + 1, dtype=torch.int64, device=dev)
     row_status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
     end = torch.zeros(3, dtype=torch.int64, device=dev)
@@ -626,9 +665,8 @@ def table_range_rows(file, table, positions, block_off, base=None, into=None, ca
 
     def plan(block_cap, row_cap):
         ws = _workspace(lib().lsm_table_range_rows_workspace_size(n, block_cap, row_cap), dev, stream)
-        _check(lib().lsm_table_range_rows_plan(*head, block_cap, row_cap, _ptr(base), _ptr(run_start), _ptr(end),
-                                               _ptr(need), _ptr(row_status), _ptr(plan_result), _ptr(ws),
-                                               ws.numel(), st), "lsm_table_range_rows_plan")
+        _check(getattr(lib(), plan_fn)(*head, block_cap, row_cap, _ptr(base), _ptr(run_start), _ptr(end), _ptr(need),
+                                       _ptr(row_status), _ptr(plan_result), _ptr(ws), ws.numel(), st), plan_fn)
         return ws
 
     trim = None
@@ -657,10 +695,10 @@ def table_range_rows(file, table, positions, block_off, base=None, into=None, ca
         key_cap, val_cap = int(caps[2]), int(caps[3])
         dst = _mi_alloc(dev, item_cap, key_cap, val_cap)
     ws = plan(block_cap, row_cap)
-    _check(lib().lsm_table_range_rows(*head, block_cap, row_cap, _ptr(base), _ptr(end), _ptr(ws), ws.numel(),
-                                      _ptr(dst["key_off"]), _ptr(dst["val_off"]), _ptr(dst["keys"]), key_cap,
-                                      _ptr(dst["vals"]), val_cap, _ptr(dst["seqno"]), _ptr(dst["vtype"]), item_cap,
-                                      _ptr(result), st), "lsm_table_range_rows")
+    _check(getattr(lib(), rows_fn)(*head, block_cap, row_cap, _ptr(base), _ptr(end), _ptr(ws), ws.numel(),
+                                   _ptr(dst["key_off"]), _ptr(dst["val_off"]), _ptr(dst["keys"]), key_cap,
+                                   _ptr(dst["vals"]), val_cap, _ptr(dst["seqno"]), _ptr(dst["vtype"]), item_cap,
+                                   _ptr(result), st), rows_fn)
     items = _items_view(dst, trim)
     items.update(run_start=run_start, row_status=row_status[:n], end=end, need=need, result=result,
                  plan_result=plan_result)
@@ -926,6 +964,37 @@ def decode_lz4_blocks(blocks, block_off, n_blocks=None, expect_type=-1, item_cap
         out["status"] = torch.where(zst[:max(n, 1)] != 0, zst[:max(n, 1)], out["status"])
     out["frames"], out["frame_off"] = frames, frame_off
     return out
+
+
+def table_frames(file, table, block_off=None, max_block_bytes=LZ4_MAX_BLOCK, stream=None):
+    """The view the framed readers take of an LZ4 table (lsm_table_frames): every data block of
+    the table inflated once, a fully populated block cache of one table.  file / table as
+    table_get; block_off: the data blocks' stored offsets, int64 cuda [n_blocks + 1] (write_table's
+    block_off; default table_block_offsets(file, table)).  lsm_lz4_plan_framed and
+    lsm_lz4_decompress_framed run over them; the plan's total is read back to size the arena (the
+    one host synchronisation).  Returns dict(stored_off, frames (padded uint8), frame_off (int64
+    [n_blocks + 1]), status (int32 [n_blocks], the decompress statuses), n_blocks, frames_len), what
+    table_get / table_range / table_range_rows take as frames= and range_read as a table's
+    "frames".  A table whose data blocks are not LZ4 yields non-OK statuses."""
+    torch = _torch()
+    if block_off is None:
+        block_off = table_block_offsets(file, table)
+    n = int(block_off.numel()) - 1
+    dev = file.device
+    frame_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    if n:
+        pws = _workspace(lib().lsm_lz4_plan_workspace_size(n), dev, stream)
+        _check(lib().lsm_lz4_plan_framed(_ptr(file), _ptr(block_off), n, max_block_bytes, _ptr(frame_off), _ptr(pws),
+                                         pws.numel(), _stream(stream)), "lsm_lz4_plan_framed")
+    total = _read_back(frame_off[-1], stream) if n else 0
+    frames = padded_bytes(total, dev)
+    status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    ws = _workspace(lib().lsm_lz4_workspace_size(n), dev, stream)
+    _check(lib().lsm_lz4_decompress_framed(_ptr(file), _ptr(block_off), n, _ptr(frames), _ptr(frame_off),
+                                           _ptr(status), _ptr(ws), ws.numel(), _stream(stream)),
+           "lsm_lz4_decompress_framed")
+    return {"stored_off": block_off, "frames": frames, "frame_off": frame_off, "status": status[:n], "n_blocks": n,
+            "frames_len": total}
 
 
 def lz4_compress_blocks(blocks, block_off, n_blocks=None, in_status=None, out_cap=None, stream=None,
@@ -1265,7 +1334,9 @@ def range_read(tables, lo, lo_off, hi, hi_off, flags, snapshot, group_seqno=None
     merge_read with the tables as sources (tables[0] is the lowest source: of equal (key, seqno)
     its row comes first) and the rows calls' row_status as in_status.  tables: dicts as
     table_range takes them, with file (padded uint8 cuda tensor), block_off (int64 cuda
-    [n_blocks + 1]) and optionally global_seqno: what write_table returns.  lo / lo_off / hi /
+    [n_blocks + 1]) and optionally global_seqno: what write_table returns.  A table whose data
+    blocks are LZ4 also carries frames (table_frames' view of it) and is read through the framed
+    calls, so one read can mix LZ4 and plain tables.  lo / lo_off / hi /
     hi_off / flags: the bounds of the n ranges, as table_range.  Returns merge_read's dict
     (n_groups = n, n_sources = len(tables)) plus row_status (int32 [len(tables) * n]).
     One host synchronisation: the rows calls' sizes are read back to size the arenas."""
@@ -1279,18 +1350,19 @@ def range_read(tables, lo, lo_off, hi, hi_off, flags, snapshot, group_seqno=None
         if start is None:  # (only table_range's row window reads it, which is not used here)
             start = torch.zeros(nb + 1, dtype=torch.int32, device=dev)
         pos = table_range(t["file"], t, lo, lo_off, hi, hi_off, flags,
-                          scan={"block_off": t["block_off"], "n_blocks": nb, "item_start": start}, stream=stream)
+                          scan={"block_off": t["block_off"], "n_blocks": nb, "item_start": start}, stream=stream,
+                          frames=t.get("frames"))
         positions.append(pos)
         # a plan with no room for rows: its need sizes the real call (pairs beyond the cap: only need[0] counts)
         cap = min(n * nb, RANGE_ROWS_AUTO_PAIRS)
         needs.append((cap, table_range_rows(t["file"], t, pos, t["block_off"], caps=(cap, 0, 0, 0), stream=stream,
-                                            n_queries=n)["need"]))
+                                            n_queries=n, frames=t.get("frames"))["need"]))
     needs = [(cap, _read_back(need, stream)) for cap, need in needs]
     for s, (cap, need) in enumerate(needs):
         if need[0] > cap:
             t = tables[s]
             again = table_range_rows(t["file"], t, positions[s], t["block_off"], caps=(need[0], 0, 0, 0),
-                                     stream=stream, n_queries=n)["need"]
+                                     stream=stream, n_queries=n, frames=t.get("frames"))["need"]
             needs[s] = (need[0], _read_back(again, stream))
     rows, key_bytes, val_bytes = (sum(need[k] for _, need in needs) for k in (1, 2, 3))
     dst = _mi_alloc(dev, rows, key_bytes, val_bytes)
@@ -1298,7 +1370,8 @@ def range_read(tables, lo, lo_off, hi, hi_off, flags, snapshot, group_seqno=None
     for s, t in enumerate(tables):
         need = needs[s][1]
         res = table_range_rows(t["file"], t, positions[s], t["block_off"], base=cursor, into=dst,
-                               caps=(need[0], need[1], key_bytes, val_bytes), stream=stream, n_queries=n)
+                               caps=(need[0], need[1], key_bytes, val_bytes), stream=stream, n_queries=n,
+                               frames=t.get("frames"))
         cursor = res["end"]
         run_start.append(res["run_start"][:n] if s + 1 < n_src else res["run_start"])
         row_status.append(res["row_status"])
